@@ -10,9 +10,13 @@ them as a captured HIP graph instead, whose per-replay cost made it 2 % slower a
 round 5's same-box A/B).
 
 Headline workload (BASELINE.json configs[1]): SF7 BW125 osr 1, 1,000,000 data symbols
-= 15,625 frames x (2 sync + 64 data) per GPU.  The SF12 configuration (configs[2]) and
-configs[4] (8 channels x 1e6 SF7 frames of 16 data symbols, one channel per GPU) are
-measured in the same run and reported under "extra", with the data-dependent slow
+= 15,625 frames x (2 sync + 64 data) per GPU.  A plain run (`--gpus 1 --steps K --warmup W`)
+sets up, warms up, times the K steps and prints the headline line; `--dump-outputs DIR`
+also writes the last timed step's outputs as DIR/<name>.npy (same arguments, same inputs:
+two builds can be compared output for output).  With `--full` the same run goes on to the
+per-kernel stage times and the roofline, parity with the exact path, the SF12
+configuration (configs[2]) and configs[4] (8 channels x 1e6 SF7 frames of 16 data
+symbols, one channel per GPU), reported under "extra", with the data-dependent slow
 rotation path (sync 0xFF), an AWGN 0 dB batch, the modulator and the CPU baselines.
 
 Multi-GPU: one process per GPU, frames sharded, no collective on the data path (weak
@@ -239,11 +243,14 @@ def stage_times(plan, iq, out, steps, device, streams=None, outs=None):
 
 def run_config(sf, frames, data_syms, steps, warmup, dist, device, snr_db=None, precision="exact",
                inputs=None, sync=None, seed_base=20251015, rank=0, window="none", osr=1, spec=True,
-               mode="legacy", streams=None):
+               mode="legacy", streams=None, stages=True, keep_last=False):
     """mode "legacy": lora_demodulate with the fused caller dechirp (the headline); "api":
     lora_phy::demodulate (phy.cpp:178-239: estimate on the raw samples, down-chirp fused per
     symbol); "raw": the detector alone per symbol (dechirp -> FFT -> argmax, the AWGN
-    script's receiver, tests/awgn_sweep.py:262-273), every symbol of the frame an output."""
+    script's receiver, tests/awgn_sweep.py:262-273), every symbol of the frame an output.
+    stages=False: the timed steps only - no per-kernel passes (stage_times) and none of the
+    roofline terms that need them (a plain run's headline).  keep_last: host copies of the
+    last timed step's outputs under "last" (--dump-outputs)."""
     import torch
 
     import lora_phy_amd as amd
@@ -309,6 +316,12 @@ def run_config(sf, frames, data_syms, steps, warmup, dist, device, snr_db=None, 
     torch.cuda.synchronize(device)
     barrier(dist)
     wall = time.perf_counter() - t0
+    last = None
+    if keep_last:
+        # what the caller of the last timed step received (step K-1 ran on stream (K-1) mod S)
+        o = out if step is not None else outs[(steps - 1) % S]
+        last = {"symbols": o.symbols.to(torch.int32).cpu(), "sync": o.sync.to(torch.int32).cpu(),
+                "cfo": o.cfo.cpu(), "time_offset": o.time_offset.cpu()}
     if step is None:
         out = outs[0]
         # every stream's outputs are the same batch's: equal to stream 0's, symbol for symbol
@@ -324,8 +337,9 @@ def run_config(sf, frames, data_syms, steps, warmup, dist, device, snr_db=None, 
     # tracer, which serialises launches, measures) - the roofline's launch time; and with the
     # steps on the timed loop's streams, where a launch shares the GPU with the other batch's
     # kernels and its wall time stretches while the step's throughput rises
-    stage_ms, out = stage_times(plan, iq, out, max(steps, 50), device)
-    stage_ms_streams = stage_ms if S == 1 else stage_times(plan, iq, out, max(steps, 50), device, sts, outs)[0]
+    if stages:
+        stage_ms, out = stage_times(plan, iq, out, max(steps, 50), device)
+        stage_ms_streams = stage_ms if S == 1 else stage_times(plan, iq, out, max(steps, 50), device, sts, outs)[0]
     total_syms = data_syms + 2
     # RAW mode demodulates every symbol of the frame (the sync symbols too)
     out_syms = total_syms if mode == "raw" else data_syms
@@ -342,6 +356,21 @@ def run_config(sf, frames, data_syms, steps, warmup, dist, device, snr_db=None, 
         ser = float((got != syms).float().mean())
     if not streams_equal:
         ser = max(ser, 1.0)  # a stream's outputs differ from stream 0's: not ok
+    if not stages:
+        # the timed figure and what follows from it alone (same keys and meaning as below)
+        step_bytes = frames * (total_syms * B_sym + 9)
+        return {
+            "sf": sf, "osr": osr, "mode": mode, "window": window, "precision": precision,
+            "frames": frames, "data_symbols": frames * out_syms, "iq_bytes": iq.numel() * 8,
+            "ms_per_step": ms_step, "symbols_ok": ser == 0.0, "ser_vs_tx": ser, "streams": S,
+            "kernels": kernels, "spec_recomputed_per_step": fixed,
+            "msym_s_data": frames * out_syms / (ms_step * 1e-3) / 1e6,
+            "msym_s_all_ranks": units / wall_max / 1e6, "ms_per_step_max_rank": wall_max * 1e3 / steps,
+            "msym_s_all": frames * total_syms / (ms_step * 1e-3) / 1e6,
+            "sync": SYNC if sync is None else sync,
+            "step_bytes": step_bytes, "pipeline_gbs": step_bytes / (ms_step * 1e-3) / 1e9,
+            "plan": plan, "iq": iq, "syms": syms, "out": out, "last": last,
+        }
     # the symbol pass in the speculative pipeline (ranks sharing a device in a rehearsal
     # can distort the stage times); otherwise the longest stage
     dom = 2 if "spec" in kernels else max(range(3), key=lambda k: stage_ms[k])
@@ -379,12 +408,35 @@ def run_config(sf, frames, data_syms, steps, warmup, dist, device, snr_db=None, 
         "sync": SYNC if sync is None else sync,
         "dominant_gbs": dom_gbs, "dominant_bytes_per_launch": dom_bytes,
         "step_bytes": step_bytes, "pipeline_gbs": step_bytes / (ms_step * 1e-3) / 1e9,
-        "plan": plan, "iq": iq, "syms": syms, "out": out,
+        "plan": plan, "iq": iq, "syms": syms, "out": out, "last": last,
     }
 
 
 def public(r):
-    return {k: v for k, v in r.items() if k not in ("plan", "iq", "syms", "out")}
+    return {k: v for k, v in r.items() if k not in ("plan", "iq", "syms", "out", "last")}
+
+
+# --dump-outputs: at most this many bytes of .npy data per run
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, last, rank=0, world=1):
+    """Write the last timed step's outputs (run_config's "last": what a caller of plan.run
+    receives - symbols [F, S], sync / cfo / time_offset [F]) as <name>.npy, float32 (every
+    value is a u16 / u8 integer or an fp32, so the conversion is exact).  Rank 0 writes
+    <name>.npy, rank r > 0 <name>.rank<r>.npy.  An output too large for its share of
+    DUMP_MAX_BYTES (all ranks' files together stay within it) is written as a fixed, seeded
+    sample of its flattened elements (sorted indices), the same from run to run."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_MAX_BYTES // world // len(last) // 4  # float32 elements per array
+    for name, t in last.items():
+        a = t.numpy().astype(np.float32)  # (int32 or fp32 host tensors)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(20251015).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + (".npy" if rank == 0 else f".rank{rank}.npy")), a)
 
 
 def _bits(t):
@@ -802,6 +854,15 @@ def main():
     # per-step time by several percent between runs of the same build
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, everything else this benchmark measures and checks: "
+                         "per-kernel stage times and the roofline, parity with the exact path, the one-stream "
+                         "figure, the HBM probe, the fast-rotation, variant, SF12, modulator and configs[4] lines "
+                         "and the CPU baselines (the --no-* options trim it).  Without it a run sets up, warms "
+                         "up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's outputs of its last timed step (symbols, sync, cfo, time_offset) "
+                         "as DIR/<name>.npy, float32")
     ap.add_argument("--frames", type=int, default=15625)
     ap.add_argument("--data-symbols", type=int, default=64)
     ap.add_argument("--sf12-frames", type=int, default=15625)
@@ -853,7 +914,42 @@ def main():
         if rank == 0:
             print(json.dumps(public(r12)))
         return
-    r7 = run_config(7, args.frames, args.data_symbols, args.steps, args.warmup, dist, device, rank=rank)
+    r7 = run_config(7, args.frames, args.data_symbols, args.steps, args.warmup, dist, device, rank=rank,
+                    stages=args.full, keep_last=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, r7["last"], rank, world)
+    workload = (f"SF7 BW125 osr1 LEGACY lora_demodulate + fused dechirp, {args.frames} frames x "
+                f"(2 sync + {args.data_symbols} data) symbols per GPU, noiseless")
+    if not args.full:
+        # a plain run: the headline alone (same metric, value, unit, ms_per_step as with --full)
+        if rank == 0:
+            line = {
+                "metric": METRIC,
+                "value": r7["msym_s_all_ranks"],
+                "unit": "Msymbols/s",
+                "n_gpus": world,
+                "steps": args.steps,
+                "warmup": args.warmup,
+                "ms_per_step": r7["ms_per_step_max_rank"],
+                "higher_is_better": True,
+                "scaling": "weak",
+                "vs_baseline": None,
+                "dtype": "f32",
+                "data": "synthetic (GPU lora_modulate of seeded random symbols, amplitude 1, no noise)",
+                "full": False,
+                "config": {"workload": workload, "launch": LAUNCH, "prewarm_ms": PREWARM_MS,
+                           "streams": r7["streams"], "sf": 7, "bw_hz": 125000, "osr": 1,
+                           "frames_per_gpu": args.frames, "data_symbols_per_frame": args.data_symbols,
+                           "parallelism": f"frames sharded x{world}, no collective (gloo timing only)",
+                           "ranks": ranks, "symbols_ok": r7["symbols_ok"], "kernels": r7["kernels"],
+                           "spec_recomputed_per_step": r7["spec_recomputed_per_step"],
+                           "msym_s_all_symbols": r7["msym_s_all"] * world,
+                           "pipeline_gbs_per_gpu": r7["pipeline_gbs"]},
+            }
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     r7["parity"] = exact_parity(r7, device)
     one = None
     if r7["streams"] > 1:
@@ -1013,8 +1109,6 @@ def main():
         except Exception as e:  # the CPU leg must not kill the GPU measurement
             log("cpu baseline failed:", e)
     if rank == 0:
-        workload = (f"SF7 BW125 osr1 LEGACY lora_demodulate + fused dechirp, {args.frames} frames x "
-                    f"(2 sync + {args.data_symbols} data) symbols per GPU, noiseless")
         line = {
             "metric": METRIC,
             "value": r7["msym_s_all_ranks"],
@@ -1028,6 +1122,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic (GPU lora_modulate of seeded random symbols, amplitude 1, no noise)",
+            "full": True,
             "config": {"workload": workload, "launch": LAUNCH, "prewarm_ms": PREWARM_MS,
                        "streams": r7["streams"], "one_stream": one, "sf": 7, "bw_hz": 125000,
                        "osr": 1,

@@ -4,6 +4,10 @@ import json
 import sys
 
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
+if "roofline" not in d:
+    # a plain run's line (no --full): the headline alone
+    print(f"SF7 {d['value']:.1f} Msym/s  {d['ms_per_step']:.4f} ms/step  symbols_ok {d['config']['symbols_ok']}")
+    sys.exit(0)
 r = d["roofline"]
 print(f"SF7 {d['value']:.1f} Msym/s  {d['ms_per_step']:.4f} ms/step  stages {[round(x, 4) for x in d['config']['stage_ms']]}  "
       f"frac {r['frac']:.4f}  pipeline {r['pipeline']['pipeline_frac']:.4f}  probe {r['hbm_probe']['d2d_copy_gbs']:.0f}")

@@ -9,7 +9,7 @@ for grp in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_AC
   i=$((i+1))
   for cfg in "--sf12-only --sf12-frames 4000" "--no-sf12 --frames 15625"; do
     tag=p${i}_$(echo $cfg | cut -c3-6)
-    timeout -k 10 -s KILL 120 rocprofv3 --pmc $grp --output-format csv -d $OUT/$tag -o run -- python bench.py --steps 2 --warmup 1 --no-cpu --no-channels $cfg > $OUT/$tag.log 2>&1 || { echo "pass $tag failed"; tail -5 $OUT/$tag.log; exit 1; }
+    timeout -k 10 -s KILL 120 rocprofv3 --pmc $grp --output-format csv -d $OUT/$tag -o run -- python bench.py --full --steps 2 --warmup 1 --no-cpu --no-channels $cfg > $OUT/$tag.log 2>&1 || { echo "pass $tag failed"; tail -5 $OUT/$tag.log; exit 1; }
   done
 done
 python tools/pmc_stalls.py $OUT

@@ -3,7 +3,7 @@
 # from the repo root; writes under gpurun_out/rec, copied by hand into profiles/rNN/):
 #   PART=tests  the whole -m gpu suite              -> pytest_gpu.log (-> pytest_gpu_summary.log)
 #   PART=only   TESTS="<pytest args>" only           -> pytest_only.log
-#   PART=bench  smoke() then `python bench.py`       -> smoke.log, bench_default.json
+#   PART=bench  smoke() then `python bench.py --full` -> smoke.log, bench_default.json
 #   PART=driver the driver's bench command           -> bench_driver.json
 #   PART=prof   bench.py under the kernel tracer (SF7 headline, SF12) and the two-rank
 #               rehearsal on one GPU                 -> bench7/, bench12/ (kernel_stats.md)
@@ -33,7 +33,7 @@ only)
 bench)
   timeout -k 10 240 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { cat $OUT/smoke.log; exit 2; }
   tail -1 $OUT/smoke.log
-  timeout -k 10 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; rc=$?
+  timeout -k 10 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; rc=$?
   tail -3 $OUT/bench_default.err
   python3 tools/bench_summary.py $OUT/bench_default.json 2>/dev/null | head -40 || head -c 2000 $OUT/bench_default.json
   exit $rc ;;
@@ -44,10 +44,10 @@ driver)
   exit $rc ;;
 prof)
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench7 -o run -- \
-    python3 bench.py --no-cpu --no-channels --no-fast --no-variants --no-sf12 > $OUT/bench7.json 2> $OUT/bench7.err || { tail -5 $OUT/bench7.err; exit 2; }
+    python3 bench.py --full --no-cpu --no-channels --no-fast --no-variants --no-sf12 > $OUT/bench7.json 2> $OUT/bench7.err || { tail -5 $OUT/bench7.err; exit 2; }
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench12 -o run -- \
     python3 bench.py --sf12-only > $OUT/bench12.json 2> $OUT/bench12.err || { tail -5 $OUT/bench12.err; exit 2; }
-  LORA_BENCH_SHARE_DEVICES=1 timeout -k 10 400 python3 bench.py --gpus 2 --no-cpu --no-channels --no-fast --no-variants --no-sf12 \
+  LORA_BENCH_SHARE_DEVICES=1 timeout -k 10 400 python3 bench.py --gpus 2 --full --no-cpu --no-channels --no-fast --no-variants --no-sf12 \
     > $OUT/bench_2ranks.json 2> $OUT/bench_2ranks.err || { tail -5 $OUT/bench_2ranks.err; exit 2; }
   tail -c 600 $OUT/bench_2ranks.json
   exit 0 ;;
@@ -62,7 +62,7 @@ trace)
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/$tag -o run -- python3 tools/prof_workload.py "$@" > $P/$tag.log 2>&1 || { tail -20 $P/$tag.log; exit 2; }
   done
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench7 -o run -- \
-    python3 bench.py --no-cpu --no-channels --no-fast --no-variants --no-sf12 > $P/bench7.json 2> $P/bench7.err || { tail -5 $P/bench7.err; exit 2; }
+    python3 bench.py --full --no-cpu --no-channels --no-fast --no-variants --no-sf12 > $P/bench7.json 2> $P/bench7.err || { tail -5 $P/bench7.err; exit 2; }
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench12 -o run -- \
     python3 bench.py --sf12-only > $P/bench12.json 2> $P/bench12.err || { tail -5 $P/bench12.err; exit 2; }
   exit 0 ;;
