@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #pragma clang fp contract(off)
 
@@ -966,11 +967,154 @@ constexpr size_t spec_lds_bytes() {
              : sizeof(cf) * ((size_t)Geo<SF>::SPW * lds_row<SF>() + demod_twl_entries<SF, true>());
 }
 
-// osr 4 in the symbol pass: whole-line loads with a lane move (1) or two half-line loads per
-// point (0, rounds 4-5)
-#ifndef LORA_OSR4_LINES
-#define LORA_OSR4_LINES 1
-#endif
+// The symbol pass's blocks (k_spec_demod), for the kernel and its launch: SPB symbols of one
+// frame per block (a wave's 64/T for T <= 64, the workgroup's SPW beyond), BPG blocks per
+// workgroup round; a frame's `per` output symbols in bpf data blocks (the last may be partial),
+// then (sync) the two sync symbols of SPB/2 consecutive frames per block.
+// (the count as a macro: the kernel needs the expression itself - taken through a function,
+// however inlined, the sync blocks' clamp compiles differently at SPB = 1 and the SF 10 / 12
+// kernels' register counts move)
+#define LORA_SPEC_BLOCKS(SPB, dblocks, frames, sync) ((dblocks) + ((sync) ? (2 * (frames) + (SPB) - 1) / (SPB) : 0))
+template <int SF>
+struct SpecGrid {
+  static constexpr int SPB = Geo<SF>::WAVE_LOCAL ? 64 / Geo<SF>::T : Geo<SF>::SPW;
+  static constexpr int BPG = Geo<SF>::WAVE_LOCAL ? 4 : 1;
+  __host__ __device__ static constexpr int bpf(int per) { return (per + SPB - 1) / SPB; }
+  // the workgroup rounds a launch has to cover
+  static constexpr int64_t groups(int64_t frames, int per, bool sync) {
+    return (LORA_SPEC_BLOCKS(SPB, frames * bpf(per), frames, sync) + BPG - 1) / BPG;
+  }
+};
+
+// A buffer resource over everything from p on (raw, no bounds: byte offsets < 2^31).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void* p) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, 0x7fffffff, 0x00020000);
+}
+
+// One data block of the symbol pass's prefetching loops (PL, PF, PF3), per lane: the frame
+// (wave-uniform), the lane's symbol and its window.  nbr (the two-pass loops): a late lane's
+// extra point comes from the next lane group; base and jl serve the variant's loads only.
+struct SpecBlk {
+  int64_t f, base;
+  int s, jl, d, cg;
+  bool valid, mis, nbr;
+  float rate;
+  int toff;
+};
+// Block bb -> B, for the lane l of slot gi.  SPM: k_spec_demod's (1 API: table phase 0; 2 RAW:
+// no offsets).  DW: samples per load line (8 or 16), d the window's offset in its line.
+// RECIP (PL): the frame bb / bpf by the reciprocal mq = ceil(2^32 / bpf) - exact while
+// dblocks * bpf < 2^32 (fdiv: the round-up multiplier's error stays below 1 / bpf) - instead
+// of a 64-bit division on the scalar unit per block.
+// mis: the wave holds a misaligned window (two-pass loops) / a late lane (three-pass).
+template <int SF, int SPM, int DW, bool RECIP>
+__device__ __forceinline__ void spec_decode(const KArgs& a, int64_t bb, int bpf, int per, int gi, int l, bool fdiv,
+                                            uint64_t mq, SpecBlk& B) {
+  constexpr int SPB = SpecGrid<SF>::SPB, S0 = SPM == 2 ? 0 : 2;
+  const __attribute__((address_space(4))) FrameParams* fps =
+      (const __attribute__((address_space(4))) FrameParams*)a.fp_spec;
+  if constexpr (RECIP)
+    B.f = fdiv ? (bpf == 1 ? bb : (int64_t)(((uint64_t)(uint32_t)bb * mq) >> 32)) : bb / bpf;
+  else
+    B.f = bb / bpf;
+  B.jl = (int)(bb - B.f * bpf) * SPB + gi;
+  B.valid = B.jl < per;
+  B.s = S0 + (B.valid ? B.jl : per - 1);  // a partial block's spare slots mirror a valid symbol
+  B.rate = SPM == 2 ? 0.0f : fps[B.f].rate;  // scalar loads (constant address space, uniform frame)
+  B.toff = SPM == 2 ? 0 : fps[B.f].t_off;
+  sym_base(B.s, Geo<SF>::N, a.frame_len, B.toff, B.base, B.cg);
+  if constexpr (SPM == 1) B.cg = 0;
+  B.d = (int)(B.base & (DW - 1));
+  B.mis = __builtin_amdgcn_readfirstlane(__ballot(Geo<SF>::NPASS == 3 ? l < B.d : B.d != 0) != 0);
+  B.nbr = false;
+}
+// (two-pass loops, a misaligned window) the late lanes' extra point is the next window's
+// first: when that window is the next lane group's (the frame's next symbol, contiguous) it
+// is taken from that group by a lane permute where the block is consumed, so the line the
+// two windows share is fetched once
+template <int SF>
+__device__ __forceinline__ bool spec_next_is_neighbour(const KArgs& a, const SpecBlk& B, int per, int gi) {
+  int64_t bnext;
+  int cgn;
+  sym_base(B.s + 1, Geo<SF>::N, a.frame_len, B.toff, bnext, cgn);
+  return gi < SpecGrid<SF>::SPB - 1 && B.jl + 1 < per && bnext == B.base + Geo<SF>::N;
+}
+
+// A window's dechirp-table pair pp (down[cg + lr + T (2 pp)], [.. + T (2 pp + 1)]) from where
+// the kernel keeps it: DTAB the whole doubled table in LDS (dq = dtab + cg + lr, any table
+// phase, two values per ds_read2_b64); DTL its phase-0 slice in LDS (dl = dtl + lr) when every
+// window of the wave is at table phase 0 (cg0: t_off = 0 frames), else - and with neither - a
+// 16-byte load of the paired table downP (rd, vt = (cg + lr) 16).
+template <int SF, bool DTAB, bool DTL>
+__device__ __forceinline__ float4 spec_table_pair(int pp, __amdgpu_buffer_rsrc_t rd, int vt, bool cg0, const cf* dq,
+                                                  const float4* dl) {
+  constexpr int N = Geo<SF>::N, T = Geo<SF>::T;
+  if constexpr (DTAB) {
+    const cf d0 = dq[2 * pp * T], d1 = dq[(2 * pp + 1) * T];
+    return float4{d0.re, d0.im, d1.re, d1.im};
+  } else if constexpr (DTL) {
+    return cg0 ? dl[pp * T]
+               : __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, vt, pp * (N + T) * 16, 0));
+  } else {
+    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, vt, pp * (N + T) * 16, 0));
+  }
+}
+// all P/2 pairs of role lr's window at table phase cg (PF, PF3)
+template <int SF, bool DTAB, bool DTL, int NP>
+__device__ __forceinline__ void spec_table(const KArgs& a, int cg, int lr, const cf* dtab, const float4* dtl,
+                                           float4 (&dt)[NP]) {
+  const __amdgpu_buffer_rsrc_t rd = raw_rsrc(a.downP);
+  const int vt = (cg + lr) * 16;
+  bool cg0 = false;
+  if constexpr (DTL && !DTAB) cg0 = __builtin_amdgcn_readfirstlane(__ballot(cg != 0) == 0);
+#pragma unroll
+  for (int pp = 0; pp < NP; ++pp) dt[pp] = spec_table_pair<SF, DTAB, DTL>(pp, rd, vt, cg0, dtab + cg + lr, dtl + lr);
+}
+// The 8-byte-load variants' points from the lane's loads ld (a misaligned window's late lanes
+// have taken load q + 1 for point q - a two-line select the callers write out: as a function
+// beside this one it cost the SF 10 / 12 kernels' schedule 2 SGPRs): the caller-side dechirp
+// (e2e_chain_test.cpp:88-93; MODE 0) with the reference's products on the table pairs dt, and
+// (MAX) the window's max(|I|,|Q|) of exactly these samples
+template <int MODE, bool MAX, int P>
+__device__ __forceinline__ float spec_dechirp_max(const v2f (&ld)[P + 1], const float4* dt, cf (&in)[P]) {
+#pragma unroll
+  for (int q = 0; q < P; ++q) in[q] = cf{ld[q].x, ld[q].y};
+  if constexpr (MODE == 0) {
+#pragma unroll
+    for (int pp = 0; pp < P / 2; ++pp) {
+      in[2 * pp] = pk_cmul_ref(in[2 * pp], cf{dt[pp].x, dt[pp].y});
+      in[2 * pp + 1] = pk_cmul_ref(in[2 * pp + 1], cf{dt[pp].z, dt[pp].w});
+    }
+  }
+  float pm = 0.0f;
+  if constexpr (MAX) {
+#pragma unroll
+    for (int q = 0; q < P; ++q) pm = amax3(pm, in[q]);
+  }
+  return pm;
+}
+
+// v_sqrt_f32: within 1 ulp, a denormal argument may give 0 (an absolute error below 2^-63);
+// the certification's E and absolute term carry it
+__device__ __forceinline__ float spec_margin(uint32_t best, uint32_t sec) {
+  return __builtin_amdgcn_sqrtf(spec_key_value(best)) - __builtin_amdgcn_sqrtf(spec_key_value(sec));
+}
+// a data symbol (s of frame f, lane l in role lr, its own best key lbest): the index from the
+// lane that holds the best key (equal best keys in two lanes: a zero margin, so the symbol is
+// recomputed and overwritten), margin and window maximum pm from lane 0
+template <int SF, int S0>
+__device__ __forceinline__ void spec_store_symbol(const KArgs& a, int64_t f, int s, int l, int lr, uint32_t lbest,
+                                                  uint32_t best, uint32_t sec, float pm) {
+  using G = Geo<SF>;
+  constexpr int NG = G::NPASS == 2 ? G::P / G::RA : G::P / G::RB;
+  constexpr int ML = G::NPASS == 2 ? G::MA_A : G::MA_B;
+  const int o = (int)(best & 15u);  // role lr's ordinal u NG + gg: bin lr + T gg + ML u
+  const uint32_t idx = (uint32_t)(lr + G::T * (o % NG) + ML * (o / NG));
+  const float margin = spec_margin(best, sec);
+  if (lbest == best && a.syms) a.syms[f * a.sym_stride + (s - S0)] = (uint16_t)idx;
+  if (l == 0)
+    reinterpret_cast<uint2*>(a.spec_marg)[f * a.total + s] = make_uint2(__float_as_uint(margin), __float_as_uint(pm));
+}
 
 // SPEC: the speculative single-read pipeline's symbol pass (lora_capi.hip): the pre-pass
 // offsets (fp_spec) on unscaled samples, and per data symbol (spec_marg, one 8-byte
@@ -1097,8 +1241,9 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
   using G = Geo<SF>;
   constexpr int N = G::N, T = G::T, P = G::P, SPW = G::SPW;
   constexpr bool WL = G::WAVE_LOCAL;
-  constexpr int SPB = WL ? 64 / T : SPW;  // symbols per block
-  constexpr int BPG = WL ? 4 : 1;         // blocks per workgroup round
+  using SG = SpecGrid<SF>;
+  constexpr int SPB = SG::SPB;  // symbols per block
+  constexpr int BPG = SG::BPG;  // blocks per workgroup round
   constexpr int NTW = demod_twl_entries<SF, true>();
   constexpr bool OSRN = OSRV != 1;
   // the rotation folded into pass 1's first stage (fft_key FOLD): where the registers allow it
@@ -1134,12 +1279,11 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
     }
     __syncthreads();
   }
-  const int bpf = (per + SPB - 1) / SPB;  // data blocks per frame
+  const int bpf = SG::bpf(per);  // data blocks per frame
   const int64_t dblocks = frames * bpf;
-  const int64_t blocks = dblocks + (SPM != 0 ? 0 : (2 * frames + SPB - 1) / SPB);
+  const int64_t blocks = LORA_SPEC_BLOCKS(SPB, dblocks, frames, SPM == 0);
   const int64_t groups = (blocks + BPG - 1) / BPG;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  typedef float v2f __attribute__((ext_vector_type(2)));
 
   // one block: SYNC = false a data block (frame-uniform), true a sync block
   // b: the block; data blocks come with b = fb bpf + rb (the loop keeps the quotient)
@@ -1186,19 +1330,18 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
       // point q of lane l is sample base + (l + T q) osr; the osr samples from it on are
       // dechirped (MODE 0: table down[cg + j], no wrap) and enter the window's maximum
       const int osr = OSRV ? OSRV : a.osr;
-      const __amdgpu_buffer_rsrc_t rx =
-          __builtin_amdgcn_make_buffer_rsrc((void*)(a.iq + fu * a.frame_stride), (short)0, 0x7fffffff, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)a.down, (short)0, 0x7fffffff, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rx = raw_rsrc(a.iq + fu * a.frame_stride);
+      const __amdgpu_buffer_rsrc_t rd = raw_rsrc(a.down);
       const int vo = rel + (int)(base + (int64_t)l * osr) * 8;
       const int vt = (cg + l * osr) * 8;
       const int so = T * osr * 8;  // bytes between a lane's points
-      if constexpr (OSRV == 4 && LORA_OSR4_LINES) {
+      if constexpr (OSRV == 4) {
         // osr 4, whole lines: load i (< 2P) covers 2T consecutive samples of the window, lane l
         // the pair base + 2T i + 2l, +1 (16 bytes; a wave instruction reads whole 128-byte
         // lines).  The points (every 4th sample) are the first of an even lane's pairs - those
         // of even i role l/2's points, those of odd i role T/2 + l/2's, which the odd lane
         // l + 1 takes by a row_shr:1 lane move: every byte read once, by one load, in whole
-        // lines (the two half-line 16-byte loads per point fetched 1.24x the window's bytes).
+        // lines (two half-line 16-byte loads per point, rounds 4-5, fetched 1.24x the window's bytes).
         const bool odd = (l & 1) != 0;
         lr = odd ? T / 2 + (l >> 1) : (l >> 1);
         const int vo2 = rel + (int)base * 8 + 16 * l;
@@ -1227,25 +1370,22 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
             }
           }
         }
-      } else if constexpr (OSRV == 2 || OSRV == 4) {
-        // the point's osr consecutive samples (and table values) two per 16-byte load: every
-        // byte of the window is fetched by exactly one load (8-byte loads of every osr-th
-        // sample, osr of them over the same lines, cost 1.31x the window's bytes at osr 2
-        // and 0.75 ms per 15,625-frame SF7 step against 0.41)
+      } else if constexpr (OSRV == 2) {
+        // the point's two consecutive samples (and table values) in one 16-byte load: every
+        // byte of the window is fetched by exactly one load (8-byte loads of every other
+        // sample, two of them over the same lines, cost 1.31x the window's bytes and 0.75 ms
+        // per 15,625-frame SF7 step against 0.41)
 #pragma unroll
         for (int q = 0; q < P; ++q) {
-#pragma unroll
-          for (int h = 0; h < OSRV / 2; ++h) {
-            const float4 y2 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, vo + 16 * h, q * so, 2 /* nt */));
-            cf y0 = cf{y2.x, y2.y}, y1 = cf{y2.z, y2.w};
-            if constexpr (MODE == 0) {
-              const float4 d2 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, vt + 16 * h, q * so, 0));
-              y0 = pk_cmul_ref(y0, cf{d2.x, d2.y});
-              y1 = pk_cmul_ref(y1, cf{d2.z, d2.w});
-            }
-            if constexpr (!SYNC) pm = amax3(amax3(pm, y0), y1);
-            if (h == 0) in[q] = y0;
+          const float4 y2 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, vo, q * so, 2 /* nt */));
+          cf y0 = cf{y2.x, y2.y}, y1 = cf{y2.z, y2.w};
+          if constexpr (MODE == 0) {
+            const float4 d2 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, vt, q * so, 0));
+            y0 = pk_cmul_ref(y0, cf{d2.x, d2.y});
+            y1 = pk_cmul_ref(y1, cf{d2.z, d2.w});
           }
+          if constexpr (!SYNC) pm = amax3(amax3(pm, y0), y1);
+          in[q] = y0;
         }
       } else {
 #pragma unroll
@@ -1272,33 +1412,30 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
     // the lane takes 17 loads and selects.  The roles permute the lanes of each symbol, so
     // the LDS accesses (and their banks) of every instruction are the same set.
     constexpr int D = T < 8 ? T : 8;
-    constexpr bool AL = true;
-    const int d = AL ? (int)(base & (D - 1)) : 0;
-    lr = AL ? ((l - d) & (T - 1)) : l;
+    const int d = (int)(base & (D - 1));
+    lr = (l - d) & (T - 1);
     v2f ld[P + 1];
-    const __amdgpu_buffer_rsrc_t rx =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(a.iq + fu * a.frame_stride), (short)0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = raw_rsrc(a.iq + fu * a.frame_stride);
     const int vo = rel + (int)(base - d + l) * 8;
     // with the caller-side dechirp's table pairs (two values per 16-byte load), issued in
     // the order the products consume them (vmcnt retires in order: a table load issued
     // after every sample would hold the first product until the last sample arrives -
     // 7 % of the SF7 demod)
     float4 dt[MODE == 0 ? P / 2 : 1];
-    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)a.downP, (short)0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rd = raw_rsrc(a.downP);
     const int vt = (cg + lr) * 16;
     // data windows are read once (nontemporal); the sync symbols, the grid's last blocks, with
     // the default policy: stage 2 re-reads symbols 0/1 right after this pass
     constexpr int AUX = SYNC ? 0 : 2;
 #pragma unroll
     for (int pp = 0; pp < P / 2; ++pp) {
-      if constexpr (MODE == 0)
-        dt[pp] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, vt, pp * (N + T) * 16, 0));
+      if constexpr (MODE == 0) dt[pp] = spec_table_pair<SF, false, false>(pp, rd, vt, false, nullptr, nullptr);
 #pragma unroll
       for (int q = 2 * pp; q < 2 * pp + 2; ++q)
         ld[q] = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rx, vo, q * T * 8, AUX));
     }
     // (only waves holding a lane l < d: for T > 64 the symbol's first wave)
-    if (AL && __builtin_amdgcn_readfirstlane(__ballot(l < d) != 0)) {
+    if (__builtin_amdgcn_readfirstlane(__ballot(l < d) != 0)) {
       // the 17th load: lanes l < d take window points; the others (whose load would fall up
       // to T samples past the window, possibly past the batch) re-read load 15's sample
       const bool late = l < d;
@@ -1307,22 +1444,9 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
 #pragma unroll
       for (int q = 0; q < P; ++q) ld[q] = late ? ld[q + 1] : ld[q];  // ascending: ld[q + 1] not yet moved
     }
-#pragma unroll
-    for (int q = 0; q < P; ++q) in[q] = cf{ld[q].x, ld[q].y};
-    // caller-side dechirp (e2e_chain_test.cpp:88-93) with the reference's products, the
-    // window's max(|I|,|Q|) of exactly these samples (data symbols: the pre-pass covered
-    // the sync windows), then the rotation
-    if constexpr (MODE == 0) {
-#pragma unroll
-      for (int pp = 0; pp < P / 2; ++pp) {
-        in[2 * pp] = pk_cmul_ref(in[2 * pp], cf{dt[pp].x, dt[pp].y});
-        in[2 * pp + 1] = pk_cmul_ref(in[2 * pp + 1], cf{dt[pp].z, dt[pp].w});
-      }
-    }
-    if constexpr (!SYNC) {
-#pragma unroll
-      for (int q = 0; q < P; ++q) pm = amax3(pm, in[q]);
-    }
+    // dechirp and the window's maximum (data symbols: the pre-pass covered the sync windows),
+    // then the rotation
+    pm = spec_dechirp_max<MODE, !SYNC>(ld, dt, in);
     }  // osr 1
     cf z[P], wz[P];
     {
@@ -1340,13 +1464,13 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
     uint32_t best = lbest, sec = (uint32_t)(lk >> 32);
     spec_reduce<SF>(best, sec, pm, tid, red3);
     if (valid) {
+      // a data symbol's stores are spec_store_symbol's, written out beside the sync symbol's
+      // (through the helper the oversampled kernels schedule differently: up to 7 VGPRs more)
       constexpr int NG = (G::NPASS == 2 ? P / G::RA : P / G::RB);
       constexpr int ML = G::NPASS == 2 ? G::MA_A : G::MA_B;
       const int o = (int)(best & 15u);  // ordinal u * NG + gg: bin = l + T gg + ML u
       const uint32_t idx = (uint32_t)(lr + T * (o % NG) + ML * (o / NG));
-      // v_sqrt_f32: within 1 ulp, a denormal argument may give 0 (an absolute error below
-      // 2^-63); the certification's E and absolute term carry it
-      const float margin = __builtin_amdgcn_sqrtf(spec_key_value(best)) - __builtin_amdgcn_sqrtf(spec_key_value(sec));
+      const float margin = spec_margin(best, sec);
       uint2* mg = reinterpret_cast<uint2*>(a.spec_marg) + f * tot + s;
       if constexpr (!SYNC) {
         if (lbest == best && a.syms) a.syms[f * a.sym_stride + (s - S0)] = (uint16_t)idx;
@@ -1358,13 +1482,11 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
     block_sync<WL>();  // the rows (and red3) are rewritten by the next round
   };
   int64_t grp0 = blockIdx.x;
-  // PF (two-pass wave-local geometries, SF 6-9): the data blocks with the next block's
-  // samples requested during this one.  Nothing in the transform is a vector load - the
-  // pass-1 positions come from a loop-invariant copy by lane permute, pass 1's twiddles are
-  // loaded with the table pairs ahead of the prefetch, pass A's are in LDS - so no wait on
-  // the current block's operands also waits for the next block's samples (vmcnt retires in
-  // order).
-  // PL (SF7 unwindowed, round 6): the PF loop with 16-byte sample loads.  A load instruction
+  // The prefetching loops (osr 1): the data blocks with the next block's samples requested
+  // during this one, so that no wait on the current block's operands also waits for the next
+  // block's samples (vmcnt retires in order).  A block is decoded by spec_decode into a SpecBlk;
+  // each loop's `issue` is that plus its loads.
+  // PL (SF7 unwindowed, round 6): 16-byte sample loads.  A load instruction
   // reads one whole 128-byte line per symbol (lane l: samples A + 2 l + 16 j and the next,
   // j < 8) instead of half a line per 8-byte load (lane l: A + l + 8 q, q < 16): half the load
   // instructions and whole-line requests (an ablation with these loads and unchanged
@@ -1377,66 +1499,35 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
   // m + 1 (the 9th: the next window's first line, from the next lane group when contiguous).
   // Rotation factors e^{i rate (r_h + 16 m)} (spec_factors_pl); the certification's bound
   // covers them (certify_list: 36 u rmax T).
-#ifndef LORA_SPEC_PAIRLD
-#define LORA_SPEC_PAIRLD 1
-#endif
-#ifndef LORA_PL_CPOL
-#define LORA_PL_CPOL 2  // nt
-#endif
-#ifndef LORA_SPEC_EARLY
-#define LORA_SPEC_EARLY 1
-#endif
-  constexpr bool PL = LORA_SPEC_PAIRLD && SF == 7 && !HANN && WL && G::NPASS == 2 && !OSRN;
+  // (the A/B switches of these choices were last in the source at c3ae5d9; measured, DESIGN.md
+  // round 6: 16-byte loads at SF7 0.220 -> 0.192 ms per pass; their cache policy nt, the default
+  // policy +9 %; the request before the table products MODE 0 -0.8 %, RAW +0.6 %)
+  constexpr bool PL = SF == 7 && !HANN && WL && G::NPASS == 2 && !OSRN;
+  // the block after this round's, b + gstride BPG: requested while block b is transformed
+  const int64_t bstep = gstride * BPG;
   if constexpr (PL) {
     static_assert(T == 8 && P == 16 && G::G1 == 2 && G::R1 == 8 && G::LOGR1 == 3 && FOLD, "SF7 geometry");
+    static_assert(MODE != 0 || (DTAB && NTW > 0), "the fused dechirp reads the staged doubled table");
     constexpr int DL = 16;  // samples per 128-byte line
     const int tid0 = threadIdx.x;
     const int g = tid0 / T;
     const int l = tid0 % T;
     const int gi = g % SPB;
-    const __attribute__((address_space(4))) FrameParams* fps =
-        (const __attribute__((address_space(4))) FrameParams*)a.fp_spec;
-    struct Blk {
-      int64_t f;
-      int s, d, cg;
-      bool valid, mis, nbr;
-      float rate;
-      int toff;
-    };
     float4 nx[P / 2 + 1];  // loads j < 8, and the 9th (late elements)
-    // a block's frame bb / bpf by a reciprocal (exact while dblocks * bpf < 2^32: the
-    // round-up multiplier's error stays below 1 / bpf) instead of a 64-bit division on the
-    // scalar unit per block
-    const bool fdiv = (uint64_t)dblocks * (uint64_t)bpf < (1ull << 32);
+    const bool fdiv = (uint64_t)dblocks * (uint64_t)bpf < (1ull << 32);  // spec_decode RECIP
     const uint64_t mq = ((1ull << 32) + (uint64_t)bpf - 1) / (uint64_t)bpf;
-    auto issue = [&](int64_t bb, Blk& B) {
-      B.f = fdiv ? (bpf == 1 ? bb : (int64_t)(((uint64_t)(uint32_t)bb * mq) >> 32)) : bb / bpf;
-      const int jl = (int)(bb - B.f * bpf) * SPB + gi;
-      B.valid = jl < per;
-      B.s = S0 + (B.valid ? jl : per - 1);
-      B.rate = RAWM ? 0.0f : fps[B.f].rate;  // scalar loads (constant address space, uniform frame)
-      B.toff = RAWM ? 0 : fps[B.f].t_off;
-      int64_t base;
-      sym_base(B.s, N, a.frame_len, B.toff, base, B.cg);
-      if constexpr (API) B.cg = 0;
-      B.d = (int)(base & (DL - 1));
-      B.mis = __builtin_amdgcn_readfirstlane(__ballot(B.d != 0) != 0);
-      const __amdgpu_buffer_rsrc_t rx =
-          __builtin_amdgcn_make_buffer_rsrc((void*)(a.iq + B.f * a.frame_stride), (short)0, 0x7fffffff, 0x00020000);
-      const int vo = (int)(base - B.d) * 8 + 16 * l;
+    auto issue = [&](int64_t bb, SpecBlk& B) {
+      spec_decode<SF, SPM, DL, true>(a, bb, bpf, per, gi, l, fdiv, mq, B);
+      const __amdgpu_buffer_rsrc_t rx = raw_rsrc(a.iq + B.f * a.frame_stride);
+      const int vo = (int)(B.base - B.d) * 8 + 16 * l;
 #pragma unroll
       for (int j = 0; j < P / 2; ++j)
-        nx[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, vo, j * DL * 8, LORA_PL_CPOL));
-      B.nbr = false;
+        nx[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, vo, j * DL * 8, 2 /* nt */));
       if (B.mis) {
-        // the late elements' 9th line is the next window's first: when that window is the next
-        // group's (the frame's next symbol, contiguous), taken from it by a lane permute where
-        // the block is consumed; else each late element's own 8-byte load (the line's other
-        // half may lie past the window, past the batch)
-        int64_t bnext;
-        int cgn;
-        sym_base(B.s + 1, N, a.frame_len, B.toff, bnext, cgn);
-        B.nbr = gi < SPB - 1 && jl + 1 < per && bnext == base + N;
+        // the late elements' 9th line: the next group's first (spec_next_is_neighbour), else
+        // each late element's own 8-byte load (the line's other half may lie past the window,
+        // past the batch)
+        B.nbr = spec_next_is_neighbour<SF>(a, B, per, gi);
         if (!B.nbr) {
           if (2 * l < B.d) {
             const v2f e0 = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rx, vo, (P / 2) * DL * 8, 2));
@@ -1452,10 +1543,10 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
       }
     };
     int64_t b = grp0 * BPG + wave;
-    Blk nb{};
+    SpecBlk nb{};
     if (b < dblocks) issue(b, nb);
-    for (; b < dblocks; b += gstride * BPG, grp0 += gstride) {
-      const Blk B = nb;
+    for (; b < dblocks; b += bstep, grp0 += gstride) {
+      const SpecBlk B = nb;
       float4(&ld)[P / 2 + 1] = nx;  // this block's samples, consumed in place
       const int d = B.d;
       // the residues of the lane's two elements
@@ -1500,10 +1591,10 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
       // the next block's samples, requested once this block's are in registers of their own:
       // before the table products with the fused dechirp (MODE 0: SF7 pass -0.8 %), after
       // the rotation otherwise (the RAW pass gained nothing there: +0.6 %)
-      constexpr bool EARLY = LORA_SPEC_EARLY && MODE == 0;
+      constexpr bool EARLY = MODE == 0;
       if constexpr (EARLY) {
         __builtin_amdgcn_sched_barrier(0);
-        if (b + gstride * BPG < dblocks) issue(b + gstride * BPG, nb);
+        if (b + bstep < dblocks) issue(b + bstep, nb);
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (MODE == 0) {
@@ -1523,7 +1614,7 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
       asm volatile("" : "+v"(pm));
       if constexpr (!EARLY) {
         __builtin_amdgcn_sched_barrier(0);
-        if (b + gstride * BPG < dblocks) issue(b + gstride * BPG, nb);
+        if (b + bstep < dblocks) issue(b + bstep, nb);
         __builtin_amdgcn_sched_barrier(0);
       }
       // the residues' pass-1 positions: rev[r] >> 3 at N = 128 (kissfft radices 4, 4, 4, 2:
@@ -1536,263 +1627,88 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
       const uint32_t lbest = (uint32_t)lk;
       uint32_t best = lbest, sec = (uint32_t)(lk >> 32);
       spec_reduce<SF>(best, sec, pm, tid0, red3);
-      if (B.valid) {
-        constexpr int NG = P / G::RA;
-        constexpr int ML = G::MA_A;
-        const int o = (int)(best & 15u);
-        const uint32_t idx = (uint32_t)(l + T * (o % NG) + ML * (o / NG));
-        const float margin = __builtin_amdgcn_sqrtf(spec_key_value(best)) - __builtin_amdgcn_sqrtf(spec_key_value(sec));
-        if (lbest == best && a.syms) a.syms[B.f * a.sym_stride + (B.s - S0)] = (uint16_t)idx;
-        if (l == 0)
-          reinterpret_cast<uint2*>(a.spec_marg)[B.f * tot + B.s] = make_uint2(__float_as_uint(margin), __float_as_uint(pm));
-      }
+      if (B.valid) spec_store_symbol<SF, S0>(a, B.f, B.s, l, l, lbest, best, sec, pm);
       wave_sync();  // the rows are rewritten by the next round
     }
   }
-  constexpr bool PF = WL && G::NPASS == 2 && !OSRN && !PL;
-  if constexpr (PF) {
-    constexpr int D = T < 8 ? T : 8;
-    const int tid0 = threadIdx.x;
-    const int g = SPW == 1 ? 0 : tid0 / T;
-    const int l = tid0 % T;
-    const int gi = g % SPB;
-    const int lane0 = (int)(__lane_id()) - l;  // the symbol's first lane in the wave
-    int cown[G::G1];  // pass-1 positions of role l
-#pragma unroll
-    for (int h = 0; h < G::G1; ++h) cown[h] = (int)(a.rev[l + T * h] >> G::LOGR1);
-    const __attribute__((address_space(4))) FrameParams* fps =
-        (const __attribute__((address_space(4))) FrameParams*)a.fp_spec;
-    // the prefetched block: frame (uniform), symbol, window, alignment, samples
-    struct Blk {
-      int64_t f;
-      int s, d, cg;
-      bool valid, mis, nbr;
-      float rate;
-      int toff;
-    };
-    v2f nx[P + 1];
-    auto issue = [&](int64_t bb, Blk& B) {
-      B.f = bb / bpf;
-      const int jl = (int)(bb - B.f * bpf) * SPB + gi;
-      B.valid = jl < per;
-      B.s = S0 + (B.valid ? jl : per - 1);
-      B.rate = RAWM ? 0.0f : fps[B.f].rate;  // scalar loads (constant address space, uniform frame)
-      B.toff = RAWM ? 0 : fps[B.f].t_off;
-      int64_t base;
-      sym_base(B.s, N, a.frame_len, B.toff, base, B.cg);
-      if constexpr (API) B.cg = 0;
-      B.d = (int)(base & (D - 1));
-      B.mis = __builtin_amdgcn_readfirstlane(__ballot(B.d != 0) != 0);
-      const __amdgpu_buffer_rsrc_t rx =
-          __builtin_amdgcn_make_buffer_rsrc((void*)(a.iq + B.f * a.frame_stride), (short)0, 0x7fffffff, 0x00020000);
-      const int vo = (int)(base - B.d + l) * 8;
-#ifdef LORA_ABL_LD16
-      // ablation (results invalid): the window's bytes in 16-byte loads, whole lines per symbol
-      {
-        const int vo2 = (int)(base - B.d) * 8 + 16 * l;
-#pragma unroll
-        for (int pp = 0; pp < P / 2; ++pp) {
-          const float4 v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, vo2, pp * 2 * T * 8, 2));
-          nx[2 * pp] = v2f{v.x, v.y};
-          nx[2 * pp + 1] = v2f{v.z, v.w};
-        }
-      }
-#else
-#pragma unroll
-      for (int q = 0; q < P; ++q)
-        nx[q] = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rx, vo, q * T * 8, 2 /* nt */));
-#endif
-      B.nbr = false;
-      if (B.mis) {
-        // a late lane's 17th point is the next window's first: when that window is the next
-        // group's (the frame's next symbol, contiguous), taken from it by a lane permute
-        // where the block is consumed, so the line the two windows share is fetched once
-        int64_t bnext;
-        int cgn;
-        sym_base(B.s + 1, N, a.frame_len, B.toff, bnext, cgn);
-        B.nbr = gi < SPB - 1 && jl + 1 < per && bnext == base + N;
-        if (l < B.d && !B.nbr)
-          nx[P] = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rx, vo, P * T * 8, 2 /* nt */));
-      }
-    };
-    int64_t b = grp0 * BPG + wave;
-    Blk nb{};
-    if (b < dblocks) issue(b, nb);
-    for (; b < dblocks; b += gstride * BPG, grp0 += gstride) {
-      const Blk B = nb;
-      v2f(&ld)[P + 1] = nx;  // this block's samples, consumed in place (no copy per round)
-      const int d = B.d;
-      const int lr = (l - d) & (T - 1);
-      // this block's table pairs and pass 1's twiddles, then the next block's samples
-      float4 dt[MODE == 0 ? P / 2 : 1];
-      if constexpr (MODE == 0) {
-        const __amdgpu_buffer_rsrc_t rd =
-            __builtin_amdgcn_make_buffer_rsrc((void*)a.downP, (short)0, 0x7fffffff, 0x00020000);
-        const int vt = (B.cg + lr) * 16;
-        if constexpr (DTAB) {
-          // any table phase from the staged table: down[cg + lr + T q], two per ds_read2_b64
-          const cf* dq = dtab + B.cg + lr;
-#pragma unroll
-          for (int pp = 0; pp < P / 2; ++pp) {
-            const cf d0 = dq[2 * pp * T], d1 = dq[(2 * pp + 1) * T];
-            dt[pp] = float4{d0.re, d0.im, d1.re, d1.im};
-          }
-        } else {
-        // every window of the wave at table phase 0 (t_off = 0 frames): the LDS slice
-        const bool cg0 = __builtin_amdgcn_readfirstlane(__ballot(B.cg != 0) == 0);
-#pragma unroll
-        for (int pp = 0; pp < P / 2; ++pp)
-          dt[pp] = cg0 ? dtl[pp * T + lr]
-                       : __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, vt, pp * (N + T) * 16, 0));
-        }
-      }
-
-      // select (a misaligned window), dechirp, window max
-      if (B.mis) {
-        const bool late = l < d;
-        // the next group's first point (lane + T), before any lane shifts its points
-        const int src = ((int)__lane_id() + T) & 63;
-        const v2f n0 = {__shfl(ld[0].x, src, 64), __shfl(ld[0].y, src, 64)};
-        if (late && B.nbr) ld[P] = n0;
-#pragma unroll
-        for (int q = 0; q < P; ++q) ld[q] = late ? ld[q + 1] : ld[q];
-      }
-      cf in[P];
-#pragma unroll
-      for (int q = 0; q < P; ++q) in[q] = cf{ld[q].x, ld[q].y};
-      if constexpr (MODE == 0) {
-#pragma unroll
-        for (int pp = 0; pp < P / 2; ++pp) {
-          in[2 * pp] = pk_cmul_ref(in[2 * pp], cf{dt[pp].x, dt[pp].y});
-          in[2 * pp + 1] = pk_cmul_ref(in[2 * pp + 1], cf{dt[pp].z, dt[pp].w});
-        }
-      }
-      float pm = 0.0f;
-#pragma unroll
-      for (int q = 0; q < P; ++q) pm = amax3(pm, in[q]);
-      asm volatile("" : "+v"(pm));
-      cf z[P], wz[P];
-      {
-        v2f F[P];
-        spec_factors<SF>(B.rate, lr, F);
-        spec_rotate_place<SF, HANN, FOLD>(in, z, F, a.win, lr, wz);
-      }
-      asm volatile("" : "+v"(pm));
-      // the next block's samples, requested once this block's are consumed (their registers
-      // are free again)
-      __builtin_amdgcn_sched_barrier(0);
-      if (b + gstride * BPG < dblocks) issue(b + gstride * BPG, nb);
-      __builtin_amdgcn_sched_barrier(0);
-      // role lr's pass-1 positions from the lane that holds them (lane permute, no memory)
-      int cpre[G::G1];
-#pragma unroll
-      for (int h = 0; h < G::G1; ++h) cpre[h] = __shfl(cown[h], lane0 + lr, 64);
-      const uint64_t lk = fft_key<SF, false, true, (NTW > 0), true, true, NoHook, FOLD>(
-          z, rows + (size_t)g * rowc, lr, a, nullptr, twl, cpre, NoHook{}, nullptr, wz);
-      const uint32_t lbest = (uint32_t)lk;
-      uint32_t best = lbest, sec = (uint32_t)(lk >> 32);
-      spec_reduce<SF>(best, sec, pm, tid0, red3);
-      if (B.valid) {
-        constexpr int NG = P / G::RA;
-        constexpr int ML = G::MA_A;
-        const int o = (int)(best & 15u);
-        const uint32_t idx = (uint32_t)(lr + T * (o % NG) + ML * (o / NG));
-        const float margin = __builtin_amdgcn_sqrtf(spec_key_value(best)) - __builtin_amdgcn_sqrtf(spec_key_value(sec));
-        if (lbest == best && a.syms) a.syms[B.f * a.sym_stride + (B.s - S0)] = (uint16_t)idx;
-        if (l == 0)
-          reinterpret_cast<uint2*>(a.spec_marg)[B.f * tot + B.s] = make_uint2(__float_as_uint(margin), __float_as_uint(pm));
-      }
-      wave_sync();  // the rows are rewritten by the next round
-    }
-  }
-  // PF3 (three-pass geometries, SF 10-12): the same prefetching loop; the next block's
-  // samples are requested at pass B, after every vector load of the transform (the pass-1
-  // positions and twiddles, pass B's twiddle pairs - all older, so waiting for them never
-  // waits for the prefetch).  SF 11-12: a block is the workgroup's symbol.
-  constexpr bool PF3 = G::NPASS == 3 && !OSRN;
-  if constexpr (PF3) {
+  // PF (two-pass geometries but PL: SF 6, 8, 9, SF 7 with Hann) and PF3 (three-pass, SF 10-12;
+  // SF 11-12: a block is the workgroup's symbol): the same loop with 8-byte sample loads, lane l
+  // in role lr = (l - d) mod T (run_block's comment).  They differ in
+  //  - where the next block is requested: PF after the rotation - nothing in its transform is a
+  //    vector load (the pass-1 positions come from a loop-invariant copy by lane permute, pass
+  //    A's twiddles are in LDS), so no wait on the current block's operands also waits for the
+  //    next block's samples (vmcnt retires in order); PF3 at pass B (fft_key's hook), after
+  //    every vector load of its transform (the pass-1 positions, pass B's twiddle pairs);
+  //  - a late lane's 17th point: PF takes it from the next lane group where it can (nbr), PF3
+  //    always loads it (the other lanes of such a wave re-read load 15's sample: their load
+  //    would fall up to T samples past the window, possibly past the batch);
+  //  - the table pairs' source (spec_table_pair).
+  constexpr bool PF8 = !OSRN && !PL;
+  if constexpr (PF8) {
+    constexpr bool P3 = G::NPASS == 3;
+    static_assert(P3 || (WL && G::NPASS == 2), "two-pass geometries are wave-local");
     constexpr int D = T < 8 ? T : 8;
     const int tid0 = threadIdx.x;
     const int g = SPW == 1 ? 0 : tid0 / T;
     const int l = tid0 % T;
     const int gi = WL ? g % SPB : g;
-    const __attribute__((address_space(4))) FrameParams* fps =
-        (const __attribute__((address_space(4))) FrameParams*)a.fp_spec;
-    struct Blk {
-      int64_t f;
-      int s, d, cg;
-      bool valid, mis;
-      float rate;
-      int toff;
-    };
+    const int lane0 = (int)(__lane_id()) - l;  // the symbol's first lane in the wave
     // pass-1 positions of role l (an aligned window's roles are the lanes themselves)
     int cown[G::G1];
 #pragma unroll
     for (int h = 0; h < G::G1; ++h) cown[h] = (int)(a.rev[l + T * h] >> G::LOGR1);
-    v2f nx[P + 1];
-    auto issue = [&](int64_t bb, Blk& B) {
-      B.f = bb / bpf;
-      const int jl = (int)(bb - B.f * bpf) * SPB + gi;
-      B.valid = jl < per;
-      B.s = S0 + (B.valid ? jl : per - 1);
-      B.rate = RAWM ? 0.0f : fps[B.f].rate;
-      B.toff = RAWM ? 0 : fps[B.f].t_off;
-      int64_t base;
-      sym_base(B.s, N, a.frame_len, B.toff, base, B.cg);
-      if constexpr (API) B.cg = 0;
-      B.d = (int)(base & (D - 1));
-      B.mis = __builtin_amdgcn_readfirstlane(__ballot(l < B.d) != 0);  // waves holding late lanes
-      const __amdgpu_buffer_rsrc_t rx =
-          __builtin_amdgcn_make_buffer_rsrc((void*)(a.iq + B.f * a.frame_stride), (short)0, 0x7fffffff, 0x00020000);
-      const int vo = (int)(base - B.d + l) * 8;
+    v2f nx[P + 1];  // the prefetched block's samples
+    auto issue = [&](int64_t bb, SpecBlk& B) {
+      spec_decode<SF, SPM, D, false>(a, bb, bpf, per, gi, l, false, 0, B);
+      const __amdgpu_buffer_rsrc_t rx = raw_rsrc(a.iq + B.f * a.frame_stride);
+      const int vo = (int)(B.base - B.d + l) * 8;
 #pragma unroll
       for (int q = 0; q < P; ++q)
         nx[q] = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rx, vo, q * T * 8, 2 /* nt */));
-      if (B.mis)
-        nx[P] = __builtin_bit_cast(
-            v2f, __builtin_amdgcn_raw_buffer_load_b64(rx, l < B.d ? vo : vo - T * 8, P * T * 8, 2 /* nt */));
+      if (B.mis) {
+        if constexpr (P3) {
+          nx[P] = __builtin_bit_cast(
+              v2f, __builtin_amdgcn_raw_buffer_load_b64(rx, l < B.d ? vo : vo - T * 8, P * T * 8, 2 /* nt */));
+        } else {
+          B.nbr = spec_next_is_neighbour<SF>(a, B, per, gi);
+          if (l < B.d && !B.nbr)
+            nx[P] = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rx, vo, P * T * 8, 2 /* nt */));
+        }
+      }
     };
     int64_t b = grp0 * BPG + (WL ? wave : 0);
-    Blk nb{};
+    SpecBlk nb{};
     if (b < dblocks) issue(b, nb);
-    for (; b < dblocks; b += gstride * BPG, grp0 += gstride) {
-      const Blk B = nb;
-      v2f(&ld)[P + 1] = nx;
+    for (; b < dblocks; b += bstep, grp0 += gstride) {
+      const SpecBlk B = nb;
+      v2f(&ld)[P + 1] = nx;  // this block's samples, consumed in place (no copy per round)
       const int d = B.d;
       const int lr = (l - d) & (T - 1);
+      // this block's table pairs, ahead of the next block's samples
       float4 dt[MODE == 0 ? P / 2 : 1];
-      if constexpr (MODE == 0) {
-        const __amdgpu_buffer_rsrc_t rd =
-            __builtin_amdgcn_make_buffer_rsrc((void*)a.downP, (short)0, 0x7fffffff, 0x00020000);
-        const int vt = (B.cg + lr) * 16;
-#pragma unroll
-        for (int pp = 0; pp < P / 2; ++pp)
-          dt[pp] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, vt, pp * (N + T) * 16, 0));
-      }
+      if constexpr (MODE == 0) spec_table<SF, DTAB, DTL>(a, B.cg, lr, dtab, dtl, dt);
+      // select (a misaligned window), dechirp, window max
       if (B.mis) {
         const bool late = l < d;
+        if constexpr (!P3) {
+          // the next group's first point (lane + T), before any lane shifts its points
+          const int src = ((int)__lane_id() + T) & 63;
+          const v2f n0 = {__shfl(ld[0].x, src, 64), __shfl(ld[0].y, src, 64)};
+          if (late && B.nbr) ld[P] = n0;
+        }
 #pragma unroll
         for (int q = 0; q < P; ++q) ld[q] = late ? ld[q + 1] : ld[q];
       }
       cf in[P];
-#pragma unroll
-      for (int q = 0; q < P; ++q) in[q] = cf{ld[q].x, ld[q].y};
-      if constexpr (MODE == 0) {
-#pragma unroll
-        for (int pp = 0; pp < P / 2; ++pp) {
-          in[2 * pp] = pk_cmul_ref(in[2 * pp], cf{dt[pp].x, dt[pp].y});
-          in[2 * pp + 1] = pk_cmul_ref(in[2 * pp + 1], cf{dt[pp].z, dt[pp].w});
-        }
-      }
-      float pm = 0.0f;
-#pragma unroll
-      for (int q = 0; q < P; ++q) pm = amax3(pm, in[q]);
-      // pass B's twiddle pairs, requested once the table pairs are consumed: they have the
+      float pm = spec_dechirp_max<MODE, true>(ld, dt, in);
+      // (PF3) pass B's twiddle pairs, requested once the table pairs are consumed: they have the
       // rotation and passes 1 and A to arrive
       constexpr int NTB = G::RB == 16 ? 15 : 3;
-      cf wb[(P / G::RB) * NTB];
+      cf wb[P3 ? (P / G::RB) * NTB : 1];
+      if constexpr (P3) {
 #pragma unroll
-      for (int gg = 0; gg < P / G::RB; ++gg) load_tw2<G::RB, G::MA_B>(wb + gg * NTB, (lr + T * gg) % G::MA_B, a.twTB2);
+        for (int gg = 0; gg < P / G::RB; ++gg) load_tw2<G::RB, G::MA_B>(wb + gg * NTB, (lr + T * gg) % G::MA_B, a.twTB2);
+      }
       asm volatile("" : "+v"(pm));
       cf z[P], wz[P];
       {
@@ -1801,31 +1717,33 @@ k_spec_demod(KArgs a, int64_t frames, int rowc, int64_t gstride) {
         spec_rotate_place<SF, HANN, FOLD>(in, z, F, a.win, lr, wz);
       }
       asm volatile("" : "+v"(pm));
-      const int64_t bn = b + gstride * BPG;
-      auto hook = [&]() {
-        if (bn < dblocks) issue(bn, nb);
+      auto prefetch = [&]() {
+        if (b + bstep < dblocks) issue(b + bstep, nb);
       };
-      // role lr's pass-1 positions: the lane's own for an aligned window, else a table load
-      // (issued before the prefetch, so waiting for it never waits for the next samples)
       int cpre[G::G1];
+      uint64_t lk;
+      if constexpr (P3) {
+        // role lr's pass-1 positions: the lane's own for an aligned window, else a table load
+        // (issued before the prefetch, so waiting for it never waits for the next samples)
 #pragma unroll
-      for (int h = 0; h < G::G1; ++h) cpre[h] = d == 0 ? cown[h] : (int)(a.rev[lr + T * h] >> G::LOGR1);
-      const uint64_t lk = fft_key<SF, false, true, (NTW > 0), true, true, decltype(hook), FOLD>(
-          z, rows + (size_t)g * rowc, lr, a, nullptr, twl, cpre, hook, wb, wz);
+        for (int h = 0; h < G::G1; ++h) cpre[h] = d == 0 ? cown[h] : (int)(a.rev[lr + T * h] >> G::LOGR1);
+        lk = fft_key<SF, false, true, (NTW > 0), true, true, decltype(prefetch), FOLD>(
+            z, rows + (size_t)g * rowc, lr, a, nullptr, twl, cpre, prefetch, wb, wz);
+      } else {
+        // the samples' registers are free again
+        __builtin_amdgcn_sched_barrier(0);
+        prefetch();
+        __builtin_amdgcn_sched_barrier(0);
+        // role lr's pass-1 positions from the lane that holds them (lane permute, no memory)
+#pragma unroll
+        for (int h = 0; h < G::G1; ++h) cpre[h] = __shfl(cown[h], lane0 + lr, 64);
+        lk = fft_key<SF, false, true, (NTW > 0), true, true, NoHook, FOLD>(
+            z, rows + (size_t)g * rowc, lr, a, nullptr, twl, cpre, NoHook{}, nullptr, wz);
+      }
       const uint32_t lbest = (uint32_t)lk;
       uint32_t best = lbest, sec = (uint32_t)(lk >> 32);
       spec_reduce<SF>(best, sec, pm, tid0, red3);
-      if (B.valid) {
-        constexpr int NG = P / G::RB;
-        constexpr int ML = G::MA_B;
-        const int o = (int)(best & 15u);
-        const uint32_t idx = (uint32_t)(lr + T * (o % NG) + ML * (o / NG));
-        const float margin =
-            __builtin_amdgcn_sqrtf(spec_key_value(best)) - __builtin_amdgcn_sqrtf(spec_key_value(sec));
-        if (lbest == best && a.syms) a.syms[B.f * a.sym_stride + (B.s - S0)] = (uint16_t)idx;
-        if (l == 0)
-          reinterpret_cast<uint2*>(a.spec_marg)[B.f * tot + B.s] = make_uint2(__float_as_uint(margin), __float_as_uint(pm));
-      }
+      if (B.valid) spec_store_symbol<SF, S0>(a, B.f, B.s, l, lr, lbest, best, sec, pm);
       block_sync<WL>();  // the rows (and red3) are rewritten by the next round
     }
   }
@@ -2727,27 +2645,24 @@ k_cert_split(KArgs a, int64_t frames, int rowc) {
   certify_list<SF, 2 * T>(a, f, q, valid, l2);
 }
 
-template <int SF, int MODE>
-bool launch_est_split(const KArgs& a, int64_t frames, hipStream_t st) {
-  using G = Geo<SF>;
-  constexpr int FPW = 64 / (2 * G::T);
-  const int rowc = row_complex<SF>();
-  const size_t lds = sizeof(cf) * (size_t)(2 * FPW) * rowc;
-  const int64_t grid = (frames + FPW - 1) / FPW;
-  launch(k_est_split<SF, MODE>, dim3((unsigned)grid), dim3(64), lds, st, a, frames, rowc);
+// launch() with dynamic LDS: refused beyond the CU's 160 KB; above the default 64 KB limit the
+// kernel's attribute is raised first.
+template <class... P, class... A>
+bool launch_lds(void (*k)(P...), int64_t grid, int block, size_t lds, hipStream_t st, A&&... args) {
+  if (lds > 160 * 1024) return false;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return false;
+  launch(k, dim3((unsigned)grid), dim3((unsigned)block), lds, st, std::forward<A>(args)...);
   return true;
 }
 
-
-template <int SF, int MODE>
-bool launch_cert_split(const KArgs& a, int64_t frames, hipStream_t st) {
-  using G = Geo<SF>;
-  constexpr int FPW = 64 / (2 * G::T);
+// k_est_split<SF, MODE> / k_cert_split<SF, MODE>: one wave per workgroup, FPW frames per wave
+template <int SF>
+bool launch_split(void (*k)(KArgs, int64_t, int), const KArgs& a, int64_t frames, hipStream_t st) {
+  constexpr int FPW = 64 / (2 * Geo<SF>::T);
   const int rowc = row_complex<SF>();
-  const size_t lds = sizeof(cf) * (size_t)(2 * FPW) * rowc;
-  const int64_t grid = (frames + FPW - 1) / FPW;
-  launch(k_cert_split<SF, MODE>, dim3((unsigned)grid), dim3(64), lds, st, a, frames, rowc);
-  return true;
+  return launch_lds(k, (frames + FPW - 1) / FPW, 64, sizeof(cf) * (size_t)(2 * FPW) * rowc, st, a, frames, rowc);
 }
 
 template <int SF, int MODE, int SPEC = 0>
@@ -2758,14 +2673,7 @@ bool launch_est_mode(const KArgs& a, int64_t frames, hipStream_t st) {
   constexpr int SPB = BLOCK / T;
   const int rowc = row_complex<SF>();
   const size_t lds = G::NPASS == 1 ? 16 : sizeof(cf) * (size_t)SPB * rowc * (EstGeo<SF>::PAIR && MODE <= 1 ? 2 : 1);
-  if (lds > 160 * 1024) return false;
-  if (lds > 64 * 1024)
-    if (hipFuncSetAttribute((const void*)k_est_fast<SF, MODE, SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return false;
-  const int64_t grid = (frames + SPB - 1) / SPB;
-  launch(k_est_fast<SF, MODE, SPEC>, dim3((unsigned)grid), dim3(BLOCK), lds, st, a, frames, rowc);
-  return true;
+  return launch_lds(k_est_fast<SF, MODE, SPEC>, (frames + SPB - 1) / SPB, BLOCK, lds, st, a, frames, rowc);
 }
 
 template <int SF>
@@ -2781,15 +2689,7 @@ bool launch_mode(const KArgs& a, int s0, int64_t work, hipStream_t st) {
   using G = Geo<SF>;
   const int rowc = row_complex<SF>();
   const size_t lds = G::NPASS == 1 ? 16 : sizeof(cf) * ((size_t)G::SPW * rowc + demod_twl_entries<SF, SPEC>());
-  if (lds > 160 * 1024) return false;
-  if (lds > 64 * 1024)
-    if (hipFuncSetAttribute((const void*)k_demod_fast<SF, MODE, FAST, SPEC>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return false;
-  const int64_t grid = (work + G::SPW - 1) / G::SPW;
-  launch(k_demod_fast<SF, MODE, FAST, SPEC>, dim3((unsigned)grid), dim3(256), lds, st, a, s0, work,
-                     rowc);
-  return true;
+  return launch_lds(k_demod_fast<SF, MODE, FAST, SPEC>, (work + G::SPW - 1) / G::SPW, 256, lds, st, a, s0, work, rowc);
 }
 
 constexpr int kSpecWgPerCu = 4;
@@ -2810,24 +2710,15 @@ int device_cus() {
 template <int SF, int MODE, bool HANN, int OSRV, int SPM = 0>
 bool launch_spec_demod_w(const KArgs& a, int64_t frames, hipStream_t st) {
   using G = Geo<SF>;
-  const int rowc = row_complex<SF>();
-  const size_t lds = spec_lds_bytes<SF>();
-  if (lds > 160 * 1024) return false;
-  if (lds > 64 * 1024)
-    if (hipFuncSetAttribute((const void*)k_spec_demod<SF, MODE, HANN, OSRV, SPM>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return false;
-  // the kernel's blocks: SPB symbols of one frame (see k_spec_demod), BPG per workgroup round
-  constexpr int SPB = G::WAVE_LOCAL ? 64 / G::T : G::SPW, BPG = G::WAVE_LOCAL ? 4 : 1;
+  using SG = SpecGrid<SF>;
   const int per = a.total - (SPM == 2 ? 0 : 2);
-  const int64_t blocks = frames * (int64_t)((per + SPB - 1) / SPB) + (SPM != 0 ? 0 : (2 * frames + SPB - 1) / SPB);
-  const int64_t groups = (blocks + BPG - 1) / BPG;
+  const int64_t groups = SG::groups(frames, per, SPM == 0);
   // persistent: the wave-local geometries, and every prefetching one (PF3: SF 10-12)
   const bool persist = G::WAVE_LOCAL || (G::NPASS == 3 && a.osr == 1);
   const int64_t cap = persist ? (int64_t)device_cus() * kSpecWgPerCu : groups;
   const int64_t grid = groups < cap ? groups : cap;
-  launch(k_spec_demod<SF, MODE, HANN, OSRV, SPM>, dim3((unsigned)grid), dim3(256), lds, st, a, frames, rowc, grid);
-  return true;
+  return launch_lds(k_spec_demod<SF, MODE, HANN, OSRV, SPM>, grid, 256, spec_lds_bytes<SF>(), st, a, frames,
+                    row_complex<SF>(), grid);
 }
 // the Hann window (LoRaDemod.cpp:158-160) and oversampling as instantiations of their own:
 // the unwindowed osr-1 kernels keep no per-point branch
@@ -2850,16 +2741,10 @@ bool launch_spec_fix(const KArgs& a, int64_t frames, hipStream_t st) {
   using G = Geo<SF>;
   const int rowc = row_complex<SF>();
   const size_t lds = sizeof(cf) * (size_t)G::SPW * rowc;
-  if (lds > 160 * 1024) return false;
-  if (lds > 64 * 1024)
-    if (hipFuncSetAttribute((const void*)k_spec_fix<SF, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return false;
   const int64_t most = (frames * (int64_t)(a.total - 1) + G::SPW - 1) / G::SPW;
   const int64_t cap = (int64_t)device_cus();  // (one per CU: an empty list costs a smaller ramp)
   const int64_t grid = std::max<int64_t>(1, std::min(most, cap));
-  launch(k_spec_fix<SF, MODE>, dim3((unsigned)grid), dim3(256), lds, st, a, rowc, grid);
-  return true;
+  return launch_lds(k_spec_fix<SF, MODE>, grid, 256, lds, st, a, rowc, grid);
 }
 
 // The speculative pipeline's four launches for SF 6-12, MODE 0/1 (see lora_capi.hip).
@@ -2910,9 +2795,8 @@ bool launch_spec_sf(const KArgs& a, int64_t frames, int stage, hipStream_t st) {
       return launch_spec_fix<SF, 2>(a, frames, st);
     }
     if constexpr (SF <= 9) {
-      if (stage == 0) return a.dechirp ? launch_est_split<SF, 0>(a, frames, st) : launch_est_split<SF, 1>(a, frames, st);
-      if (stage == 2)
-        return a.dechirp ? launch_cert_split<SF, 0>(a, frames, st) : launch_cert_split<SF, 1>(a, frames, st);
+      if (stage == 0) return launch_split<SF>(a.dechirp ? k_est_split<SF, 0> : k_est_split<SF, 1>, a, frames, st);
+      if (stage == 2) return launch_split<SF>(a.dechirp ? k_cert_split<SF, 0> : k_cert_split<SF, 1>, a, frames, st);
     }
     if (stage == 3) return a.dechirp ? launch_spec_fix<SF, 0>(a, frames, st) : launch_spec_fix<SF, 1>(a, frames, st);
     if (stage == 0) return a.dechirp ? launch_est_mode<SF, 0, 1>(a, frames, st) : launch_est_mode<SF, 1, 1>(a, frames, st);
@@ -2936,55 +2820,29 @@ bool launch_sf(const KArgs& a, int s0, int64_t work, hipStream_t st) {
   return launch_mode<SF, 2>(a, s0, work, st);
 }
 
+// f(std::integral_constant<int, sf>) for LO <= sf <= HI, false for any other sf
+template <int LO, int HI, class F>
+bool dispatch_sf(int sf, F&& f) {
+  if constexpr (LO > HI)
+    return false;
+  else
+    return sf == LO ? f(std::integral_constant<int, LO>{}) : dispatch_sf<LO + 1, HI>(sf, f);
+}
+
 }  // namespace
 
 
 bool launch_spec(const KArgs& a, int64_t frames, int stage, hipStream_t st) {
-  switch (a.sf) {
-    case 6: return launch_spec_sf<6>(a, frames, stage, st);
-    case 7: return launch_spec_sf<7>(a, frames, stage, st);
-    case 8: return launch_spec_sf<8>(a, frames, stage, st);
-    case 9: return launch_spec_sf<9>(a, frames, stage, st);
-    case 10: return launch_spec_sf<10>(a, frames, stage, st);
-    case 11: return launch_spec_sf<11>(a, frames, stage, st);
-    case 12: return launch_spec_sf<12>(a, frames, stage, st);
-    default: return false;
-  }
+  return dispatch_sf<6, 12>(a.sf, [&](auto sf) { return launch_spec_sf<sf()>(a, frames, stage, st); });
 }
 
 bool launch_est_fast(const KArgs& a, int64_t frames, hipStream_t st) {
   if (a.total < 2 || a.est_only || a.mode == LORA_MODE_RAW) return false;
-  switch (a.sf) {
-    case 2: return launch_est_sf<2>(a, frames, st);
-    case 3: return launch_est_sf<3>(a, frames, st);
-    case 4: return launch_est_sf<4>(a, frames, st);
-    case 5: return launch_est_sf<5>(a, frames, st);
-    case 6: return launch_est_sf<6>(a, frames, st);
-    case 7: return launch_est_sf<7>(a, frames, st);
-    case 8: return launch_est_sf<8>(a, frames, st);
-    case 9: return launch_est_sf<9>(a, frames, st);
-    case 10: return launch_est_sf<10>(a, frames, st);
-    case 11: return launch_est_sf<11>(a, frames, st);
-    case 12: return launch_est_sf<12>(a, frames, st);
-    default: return false;
-  }
+  return dispatch_sf<2, 12>(a.sf, [&](auto sf) { return launch_est_sf<sf()>(a, frames, st); });
 }
 
 bool launch_demod_fast(const KArgs& a, int s0, int64_t work, hipStream_t st) {
-  switch (a.sf) {
-    case 2: return launch_sf<2>(a, s0, work, st);
-    case 3: return launch_sf<3>(a, s0, work, st);
-    case 4: return launch_sf<4>(a, s0, work, st);
-    case 5: return launch_sf<5>(a, s0, work, st);
-    case 6: return launch_sf<6>(a, s0, work, st);
-    case 7: return launch_sf<7>(a, s0, work, st);
-    case 8: return launch_sf<8>(a, s0, work, st);
-    case 9: return launch_sf<9>(a, s0, work, st);
-    case 10: return launch_sf<10>(a, s0, work, st);
-    case 11: return launch_sf<11>(a, s0, work, st);
-    case 12: return launch_sf<12>(a, s0, work, st);
-    default: return false;
-  }
+  return dispatch_sf<2, 12>(a.sf, [&](auto sf) { return launch_sf<sf()>(a, s0, work, st); });
 }
 
 }  // namespace lora

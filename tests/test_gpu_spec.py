@@ -529,6 +529,9 @@ def test_sf7_whole_line_pass_every_line_offset(O, amd, dechirp, snr_db):
         toffs.add(int(round(float(otoff))) % 16)
     if snr_db is None:
         assert len(toffs) >= 12, toffs  # the line offsets the frames exercised
+        fixed = plan.spec_recomputed()
+        print(f"RECOMPUTED whole-line dechirp={dechirp}: {fixed}")
+        assert fixed <= PL_RECOMPUTED[dechirp]
 
 
 @pytest.mark.parametrize("osr,window", [(1, "none"), (2, "none"), (4, "none"), (1, "hann")])
@@ -559,3 +562,134 @@ def test_frames_at_unaligned_addresses(O, amd, osr, window):
         np.testing.assert_array_equal(syms[f], osym, err_msg=f"frame {f}")
         assert int(res.sync[f]) == osync
         assert bits(res.cfo[f].item()) == bits(ocfo) and bits(res.time_offset[f].item()) == bits(otoff)
+
+
+# ---- every window offset through the 8-byte-load loops (PF: SF 6, 8, 9 and Hann SF 7; PF3:
+# SF 10-12), the counterpart of test_sf7_whole_line_pass_every_line_offset
+
+# (sf, window, data symbols per frame, frames): the data symbols are no multiple of the block
+# (64 / T symbols of one frame: 16, 8, 4, 2, 1 at SF 6-10; the workgroup's 2 / 1 at SF 11 / 12),
+# so every frame ends in a partial block and a misaligned window's 17th point comes both ways:
+# from the next lane group (lane permute) and from the lane's own load (a wave's last group,
+# the frame's last symbol)
+OFFSET_CASES = [(6, "none", 21, 24), (7, "hann", 21, 24), (8, "none", 9, 24), (9, "none", 7, 24),
+                (10, "none", 7, 24), (11, "none", 5, 16), (12, "none", 5, 16)]
+
+# plan.spec_recomputed() of the noiseless cases on the commit before the symbol pass's loops were
+# folded into shared helpers (identical seeded inputs, deterministic kernels): (sf, dechirp) ->
+# count.  A broken pass would hide behind the exact recompute; the count shows it.
+OFFSET_RECOMPUTED = {(sf, dechirp): 0 for sf in (6, 8, 9, 10, 11, 12) for dechirp in (True, False)}
+OFFSET_RECOMPUTED.update({(7, True): 1, (7, False): 1})  # Hann SF7: one symbol, both inputs
+# ... and of test_sf7_whole_line_pass_every_line_offset's noiseless cases: dechirp -> count
+PL_RECOMPUTED = {True: 1, False: 0}
+
+
+def offset_frames(O, sf, S, F, snr_db, seed):
+    """F frames (S data symbols) whose windows start at every offset 0..7 of a 64-byte chunk:
+    sample delays and advances 0..15 and a fractional carrier offset per frame from -0.5 to
+    +0.5 bin (the estimate's time offset is -frac N, LoRaDemod.cpp:127-131)."""
+    N = 1 << sf
+    rng = np.random.default_rng(seed)
+    L = (S + 2) * N
+    iq = np.zeros((F, L), np.complex64)
+    n = np.arange(L)
+    for f in range(F):
+        syms = rng.integers(0, N, S).astype(np.uint16)
+        x = O.lora_modulate(syms, sf, 1, 125000, 1.0, int(rng.integers(0, 256)))[:L]
+        d = f % 8 + 8 * (f // 8 % 2)
+        x = np.concatenate([np.zeros(d, np.complex64), x])[:L] if f % 3 else np.concatenate([x[d:], np.zeros(d, np.complex64)])
+        # (constants chosen on the oracle so that every offset 0..7 occurs at every SF)
+        x = x * np.exp(2j * np.pi * ((0.34 + 0.9443 * f) % 1.0 - 0.5) * n / N)
+        if snr_db is not None:
+            sigma = 10.0 ** (-snr_db / 20.0) / np.sqrt(2.0)
+            x = x + sigma * (rng.standard_normal(L) + 1j * rng.standard_normal(L))
+        iq[f] = x.astype(np.complex64)
+    return iq
+
+
+@pytest.fixture(scope="module")
+def offset_reference(O):
+    """The frames of an offset case and the oracle's outputs for them, computed once."""
+    cache = {}
+
+    def get(sf, window, S, F, snr_db):
+        key = (sf, snr_db)
+        if key not in cache:
+            iq = offset_frames(O, sf, S, F, snr_db, 8800 + 10 * sf + (0 if snr_db is None else 1))
+            dech = np.stack([O.dechirp(iq[f], sf) for f in range(F)]).astype(np.complex64)
+            ref = [O.lora_demodulate(dech[f], sf, 1, window == "hann") for f in range(F)]
+            for a in (iq, dech):
+                a.setflags(write=False)
+            cache[key] = (iq, dech, ref)
+        return cache[key]
+
+    return get
+
+
+@pytest.mark.parametrize("dechirp", [True, False])
+@pytest.mark.parametrize("snr_db", [None, 0.0])
+@pytest.mark.parametrize("sf,window,S,F", OFFSET_CASES)
+def test_every_window_offset_through_the_8_byte_loops(O, amd, offset_reference, sf, window, S, F, snr_db, dechirp):
+    """The prefetching symbol-pass loops with 8-byte sample loads (k_spec_demod PF: SF 6, 8, 9
+    and SF 7 with Hann; PF3: SF 10-12) at every window offset d = 0..7 within a 64-byte chunk,
+    with the fused dechirp and on dechirped input, partial last blocks, the neighbour's line by
+    lane permute and by the lane's own 17th load: every symbol, sync word and cfo / time_offset
+    bit against the oracle, and (noiseless) no more recomputed symbols than before the loops
+    shared their helpers."""
+    iq, dech, ref = offset_reference(sf, window, S, F, snr_db)
+    plan = amd.DemodPlan(sf, 1, 125000, window, dechirp=dechirp)
+    res = plan.run(torch.from_numpy((iq if dechirp else dech).copy()).cuda())  # the shared arrays are read-only
+    torch.cuda.synchronize()
+    assert plan.last_kernels() == SPEC
+    syms = res.symbols.cpu().numpy()
+    sync, cfo, toff = res.sync.cpu().numpy(), res.cfo.cpu().numpy(), res.time_offset.cpu().numpy()
+    offs = set()
+    for f in range(F):
+        osym, osync, ocfo, otoff = ref[f]
+        np.testing.assert_array_equal(syms[f], osym, err_msg=f"frame {f}")
+        assert int(sync[f]) == osync, f"frame {f} sync"
+        assert bits(cfo[f]) == bits(ocfo) and bits(toff[f]) == bits(otoff), f"frame {f}"
+        offs.add(int(round(float(otoff))) % 8)
+    if snr_db is None:
+        assert offs == set(range(8)), offs  # the chunk offsets the frames exercised
+        fixed = plan.spec_recomputed()
+        print(f"RECOMPUTED offsets sf={sf} dechirp={dechirp}: {fixed}")
+        assert fixed <= OFFSET_RECOMPUTED[(sf, dechirp)]
+
+
+@pytest.mark.parametrize("sf,S", [(8, 5), (10, 3)])
+def test_prefetch_carries_into_a_second_persistent_round(amd, sf, S):
+    """More data blocks than one round of the persistent grid takes (4 workgroups per CU, 4
+    wave blocks each), so the prefetch issued in a block of the first round is consumed in the
+    second, partial one (SF 8: the two-pass loop; SF 10: the three-pass loop): every output
+    equal to the exact three-launch path's on the same tensor."""
+    N = 1 << sf
+    spb = 64 // (N // 16)  # symbols per block
+    bpf = -(-S // spb)  # data blocks per frame (the last one partial)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    F = -(-(4 * cus * 4 * 5 // 4) // bpf)  # one round and a quarter
+    assert 4 * cus * 4 < F * bpf < 2 * 4 * cus * 4
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device="cpu").manual_seed(500 + sf)
+    syms = torch.randint(0, N, (F, S), generator=g, dtype=torch.int32)
+    x = amd.modulate(syms.to(dev), sf)
+    L = x.shape[1]
+    n = torch.arange(L, device=dev, dtype=torch.float64)
+    frac = (torch.arange(F, device=dev, dtype=torch.float64) * 0.618) % 1.0 - 0.5
+    x = x * torch.exp(2j * np.pi * frac[:, None] * n[None, :] / N).to(torch.complex64)
+    iq = torch.zeros((F, L + 8), dtype=torch.complex64, device=dev)
+    for k in range(8):  # sample delays 0..7
+        iq[k::8, k:k + L] = x[k::8]
+    iq = iq[:, :L].contiguous()
+    del x
+    out = []
+    for spec in (True, False):
+        with amd.spec_pipeline(spec):
+            plan = amd.DemodPlan(sf, 1, 125000, "none", dechirp=True)
+        res = plan.run(iq)
+        torch.cuda.synchronize()
+        assert ("spec" in plan.last_kernels()) == spec
+        out.append((res.symbols.clone(), res.sync.clone(), res.cfo.clone(), res.time_offset.clone()))
+    for a, b in zip(*out):
+        assert torch.equal(a.view(torch.int32) if a.is_floating_point() else a,
+                           b.view(torch.int32) if b.is_floating_point() else b)
