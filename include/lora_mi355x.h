@@ -156,6 +156,64 @@ int64_t lora_mod_batch(unsigned sf, unsigned osr, unsigned bw_hz, float amplitud
                        const uint16_t* symbols, int64_t frames, int64_t sym_count, float* iq,
                        int device, void* stream);
 
+/* ---- Payload codec on the device: symbols <-> bytes for F frames per call ----------------
+ * Each call enqueues one kernel on `stream` of `device`, allocates and synchronises nothing,
+ * needs no workspace and fully writes every output it is given (no buffer has to be cleared
+ * first).  All buffers are device memory; rows are `*_stride` elements apart.  Parameters are
+ * checked before any HIP call: a NULL required buffer, sf outside 6..12, rdd outside 0..4,
+ * nbytes > 255 or a stride smaller than its row give LORA_EINVAL; frames == 0 is a no-op that
+ * returns the per-frame count.  Optional outputs (crc_ok and the counters) may be NULL. */
+
+/* lora_phy::lora_decode (phy.hpp:213-215, LoRaDecoder.cpp:8-19) for `frames` frames of
+ * `sym_count` symbols: Hamming 8/4 decode of each symbol's low byte (decodeHamming84sx,
+ * LoRaCodes.hpp:250-281), consecutive pairs giving one byte, high nibble first; an odd
+ * trailing symbol is ignored.  payload [frames][payload_stride] receives n = sym_count / 2
+ * bytes per frame.  Per frame, optionally: crc_ok[f] = 1 when n >= 4 and
+ * payload[n-2] | payload[n-1] << 8 equals sx1272DataChecksum (LoRaCodes.hpp:92-105) of
+ * payload[2 .. n-2), else 0 - the check of lora_phy::decode (phy.hpp:118-120,
+ * phy.cpp:241-256); err_count[f] / bad_count[f] = symbols whose decode raised `error` / `bad`.
+ * Returns n. */
+int64_t lora_decode_batch(const uint16_t* symbols, int64_t frames, int64_t sym_count, int64_t sym_stride,
+                          uint8_t* payload, int64_t payload_stride, uint8_t* crc_ok, int32_t* err_count,
+                          int32_t* bad_count, int device, void* stream);
+
+/* lora_phy::lora_encode (phy.hpp:209-211, LoRaEncoder.cpp:8-19) for `frames` payloads of
+ * `nbytes` bytes: each byte becomes two Hamming 8/4 codewords (encodeHamming84sx,
+ * LoRaCodes.hpp:229-242) used as symbols, high nibble first.  With append_crc != 0 the
+ * sx1272DataChecksum of payload[2 .. nbytes) follows as two more bytes, low byte first, so that
+ * lora_decode_batch reports crc_ok on the round trip.  Returns the symbols per frame,
+ * 2 * (nbytes + (append_crc ? 2 : 0)). */
+int64_t lora_encode_batch(const uint8_t* payload, int64_t frames, int64_t nbytes, int64_t payload_stride,
+                          int append_crc, uint16_t* symbols, int64_t sym_stride, int device, void* stream);
+
+/* The receive side of the coding chain around the demodulator, at coding rate 4 / (4 + rdd)
+ * and PPM = sf, the inverse of lora_encode_chain_batch: Gray -> binary (grayToBinary16,
+ * LoRaCodes.hpp:212-222), diagonal deinterleave of whole blocks of 4 + rdd symbols into sf
+ * codewords each (diagonalDeterleaveSx, LoRaCodes.hpp:396-412; trailing symbols that do not
+ * fill a block are ignored), de-whitening (Sx1272ComputeWhiteningLfsr with bit offset 0,
+ * LoRaCodes.hpp:176-189), nibble decode by rdd (Hamming 8/4, Hamming 7/4, parity 6/4, parity
+ * 5/4, the bare nibble; LoRaCodes.hpp:250-365), nibbles packed high first into `nbytes` bytes.
+ * err_count[f] (optional) = codewords among the first 2 * nbytes that flagged an error (Hamming
+ * 8/4's `bad` counts as one).  LORA_ERANGE when 2 * nbytes exceeds the codewords sym_count
+ * yields.  Returns nbytes. */
+int64_t lora_decode_chain_batch(int sf, int rdd, const uint16_t* symbols, int64_t frames, int64_t sym_count,
+                                int64_t sym_stride, int64_t nbytes, uint8_t* payload, int64_t payload_stride,
+                                int32_t* err_count, int device, void* stream);
+
+/* The transmit side of the same chain (the order of runners/lora_phy_vector_generate.cpp:
+ * 189-223): bytes -> nibbles, high first -> codewords by rdd (LoRaCodes.hpp:229-371), padded
+ * with zero codewords to a multiple of sf -> whitening (LoRaCodes.hpp:176-189) -> diagonal
+ * interleave (diagonalInterleaveSx, LoRaCodes.hpp:376-394) -> Gray (binaryToGray16,
+ * LoRaCodes.hpp:201-207).  Returns the symbols per frame (lora_chain_symbols). */
+int64_t lora_encode_chain_batch(int sf, int rdd, const uint8_t* payload, int64_t frames, int64_t nbytes,
+                                int64_t payload_stride, uint16_t* symbols, int64_t sym_stride, int device,
+                                void* stream);
+
+/* Symbols per frame of the chain for `nbytes` payload bytes: ceil(2 * nbytes / sf) * (4 + rdd)
+ * (the block count of diagonalInterleaveSx, LoRaCodes.hpp:376-394).  Host arithmetic only, no
+ * HIP call. */
+int64_t lora_chain_symbols(int sf, int rdd, int64_t nbytes);
+
 /* Measurement hooks (bench.py): while enabled, every kernel lora_demod_batch launches
  * on this plan is bracketed by a pair of HIP events on the stream it runs on, for up
  * to `max_calls` calls.  Stages: 0 = frame max, 1 = estimate + sync symbols (with the

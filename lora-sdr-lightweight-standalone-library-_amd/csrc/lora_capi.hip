@@ -72,6 +72,8 @@ using lora::PI_F;
 
 }  // namespace
 
+int lora::set_last_error(int code, const std::string& msg) { return set_error(code, msg); }
+
 // ChirpGenerator.hpp:105-132 (genChirp), float recurrence, std::polar -> sincosf.
 void lora::host_gen_chirp(std::complex<float>* out, int N, int osr, int NN, float f0, bool down,
                           float ampl, float& phase, float bw_scale) {

@@ -1,6 +1,7 @@
 // lora_internal.h — kernel argument block shared by the demod translation units.
 #pragma once
 #include <complex>
+#include <string>
 
 #include "lora_device.h"
 
@@ -105,6 +106,10 @@ __device__ __forceinline__ float frame_maxv(const KArgs& a, int64_t f) {
 // the plan's down-chirp tables and the C++ drop-in's genChirp (lora_phy_dropin.cpp).
 void host_gen_chirp(std::complex<float>* out, int N, int osr, int NN, float f0, bool down, float ampl,
                     float& phase, float bw_scale);
+
+// Record the calling thread's lora_last_error() text and return `code` (lora_capi.hip), for
+// the C-ABI entry points of the other translation units.
+int set_last_error(int code, const std::string& msg);
 
 // Fast symbol demodulator (lora_demod_fast.hip): register-blocked kissfft-exact FFT.
 // Returns false if the configuration is not covered (caller uses the generic kernel).

@@ -3,16 +3,17 @@
 Python host layer over the C-ABI of include/lora_mi355x.h (liblora_mi355x.so, HIP
 for gfx950).  IQ lives in torch.complex64 CUDA(HIP) tensors; the kernels run on the
 current torch stream.  Host-side coding helpers (Hamming, Gray, interleave,
-whitening, CRC) are in :mod:`lora_phy_amd.codes`; the phy.hpp-style functional API
-is in :mod:`lora_phy_amd.phy`.
+whitening, CRC) are in :mod:`lora_phy_amd.codes`, their batched device counterparts
+(symbols <-> payload bytes, one kernel per call) in :mod:`lora_phy_amd.codec`; the
+phy.hpp-style functional API is in :mod:`lora_phy_amd.phy`.
 """
-from . import _capi, codes, iq_io, phy, shard  # noqa: F401
+from . import _capi, codec, codes, iq_io, phy, shard  # noqa: F401
 from ._capi import LoraError
 from .demod import DemodPlan, DemodResult, LoRaDemod, compensate_offsets, spec_pipeline
 from .mod import LoRaMod, modulate
 
 __all__ = ["DemodPlan", "DemodResult", "LoRaDemod", "LoRaMod", "LoraError", "modulate",
-           "compensate_offsets", "spec_pipeline", "codes", "iq_io", "phy", "shard", "lib_path", "version", "source_hash",
+           "compensate_offsets", "spec_pipeline", "codec", "codes", "iq_io", "phy", "shard", "lib_path", "version", "source_hash",
            "check_build"]
 
 

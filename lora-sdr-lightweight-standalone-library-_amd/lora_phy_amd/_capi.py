@@ -38,6 +38,11 @@ EXPORTED_SYMBOLS = (
     "lora_mod_batch",
     "lora_estimate_offsets_batch",
     "lora_compensate_offsets_batch",
+    "lora_decode_batch",
+    "lora_encode_batch",
+    "lora_decode_chain_batch",
+    "lora_encode_chain_batch",
+    "lora_chain_symbols",
     "lora_demod_profile_enable",
     "lora_demod_profile_read",
     "lora_demod_last_kernels",
@@ -115,6 +120,21 @@ def lib() -> C.CDLL:
     L.lora_compensate_offsets_batch.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_int64,
                                                 C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p]
+    # the payload codec (csrc/lora_codec.hip)
+    L.lora_decode_batch.restype = C.c_int64
+    L.lora_decode_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.lora_encode_batch.restype = C.c_int64
+    L.lora_encode_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
+                                    C.c_int64, C.c_int, C.c_void_p]
+    L.lora_decode_chain_batch.restype = C.c_int64
+    L.lora_decode_chain_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                          C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+    L.lora_encode_chain_batch.restype = C.c_int64
+    L.lora_encode_chain_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                          C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    L.lora_chain_symbols.restype = C.c_int64
+    L.lora_chain_symbols.argtypes = [C.c_int, C.c_int, C.c_int64]
     L.lora_demod_profile_enable.restype = C.c_int
     L.lora_demod_profile_enable.argtypes = [C.c_void_p, C.c_int]
     L.lora_demod_profile_read.restype = C.c_int

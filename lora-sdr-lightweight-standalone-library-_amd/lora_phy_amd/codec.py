@@ -1,0 +1,169 @@
+"""The payload codec on the GPU: symbols <-> bytes for whole batches of frames.
+
+Torch-tensor wrappers over lora_decode_batch / lora_encode_batch / lora_decode_chain_batch /
+lora_encode_chain_batch (include/lora_mi355x.h, csrc/lora_codec.hip): one kernel per call on
+the current torch stream, nothing leaves the device.  There is no CPU fallback (TypeError on
+a CPU tensor); the host implementation of the same functions, :mod:`lora_phy_amd.codes`, is
+the checker in the tests.
+
+Symbols are uint16 tensors, payloads uint8 tensors, [F, n] or 1-D for a single frame.  Rows
+may be strided views (unit stride within a row, rows not overlapping).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import _capi, codes
+from .demod import _check_buf, _require_cuda, _stream_handle
+
+MAX_PAYLOAD = 255  # bytes per frame of the encoders and the chain decoder
+
+# the current stream's handle without building a torch.cuda.Stream object per call (a
+# microsecond of the few a call costs on the host)
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def _stream(device: torch.device) -> int:
+    return _raw_stream(device.index) if _raw_stream is not None else _stream_handle(device)
+
+
+@dataclass
+class DecodeResult:
+    """Per-frame results of one decode call (all tensors on the symbols' device)."""
+
+    payload: torch.Tensor            # [F, n] uint8
+    crc_ok: Optional[torch.Tensor]   # [F] bool: the frame's last two bytes are its data checksum
+    errors: torch.Tensor             # [F] int32: codewords whose decode flagged an error
+    bad: Optional[torch.Tensor]      # [F] int32: uncorrectable Hamming 8/4 codewords (library decoder)
+
+
+def _rows(t: torch.Tensor, name: str, dtype: torch.dtype):
+    """-> (2-D view, squeeze): device, dtype and layout the C library cannot check."""
+    _require_cuda(t, name)
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    squeeze = t.dim() == 1
+    if squeeze:
+        t = t.unsqueeze(0)
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{name} must be [frames, n] (or [n]) with unit stride within a row and "
+                         "non-overlapping rows")
+    return t, squeeze
+
+
+def _row_stride(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _symbols(t: torch.Tensor):
+    if isinstance(t, torch.Tensor) and t.dtype in (torch.int16, torch.int32, torch.int64, torch.uint8):
+        _require_cuda(t, "symbols")
+        t = t.to(torch.int32).to(torch.uint16)  # the low 16 bits, as modulate() takes them
+    return _rows(t, "symbols", torch.uint16)
+
+
+def _out_rows(out: Optional[torch.Tensor], name: str, dtype: torch.dtype, F: int, n: int, squeeze: bool,
+              device: torch.device) -> torch.Tensor:
+    if out is None:
+        return torch.empty((F, n), dtype=dtype, device=device)
+    o, _ = _rows(out, name, dtype)
+    if o.device != device or o.shape[0] != F or o.shape[1] != n or squeeze != (out.dim() == 1):
+        raise ValueError(f"{name} must be a {dtype} {'[%d]' % n if squeeze else '[%d, %d]' % (F, n)} "
+                         f"tensor on {device}")
+    return o
+
+
+def _ptr(t: torch.Tensor):
+    return t.data_ptr() if t.numel() > 0 else None
+
+
+def encode(payload: torch.Tensor, append_crc: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """lora_encode (LoRaEncoder.cpp:8-19): every byte -> two Hamming 8/4 codewords used as
+    symbols, high nibble first.  ``append_crc``: the SX1272 data checksum of ``payload[2:]``
+    follows as two more bytes (low byte first), so ``decode`` reports ``crc_ok``.
+    Returns uint16 [F, 2 * (n + 2 * append_crc)]."""
+    p, squeeze = _rows(payload, "payload", torch.uint8)
+    F, n = p.shape
+    if n > MAX_PAYLOAD:
+        raise ValueError(f"payload rows hold at most {MAX_PAYLOAD} bytes")
+    S = 2 * (n + (2 if append_crc else 0))
+    o = _out_rows(out, "out", torch.uint16, F, S, squeeze, p.device)
+    _capi.check(_capi.lib().lora_encode_batch(_ptr(p), F, n, _row_stride(p), int(bool(append_crc)), _ptr(o),
+                                              _row_stride(o), p.device.index, _stream(p.device)))
+    return o[0] if squeeze else o
+
+
+def decode(symbols: torch.Tensor, out: Optional[DecodeResult] = None) -> DecodeResult:
+    """lora_decode (LoRaDecoder.cpp:8-19) with the CRC check of lora_phy::decode
+    (phy.cpp:241-256): pairs of symbols -> bytes through Hamming 8/4 on the symbols' low byte
+    (an odd trailing symbol is ignored); per frame ``crc_ok``, and how many symbols flagged
+    ``error`` / ``bad``.  ``out``: a DecodeResult of matching tensors to write into (no
+    allocation)."""
+    s, squeeze = _symbols(symbols)
+    F, S = s.shape
+    n = S // 2
+    dev = s.device
+    if out is None:
+        out = DecodeResult(payload=torch.empty((n,) if squeeze else (F, n), dtype=torch.uint8, device=dev),
+                           crc_ok=torch.empty(F, dtype=torch.bool, device=dev),
+                           errors=torch.empty(F, dtype=torch.int32, device=dev),
+                           bad=torch.empty(F, dtype=torch.int32, device=dev))
+    pay = _out_rows(out.payload, "out.payload", torch.uint8, F, n, squeeze, dev)
+    for name, dt in (("crc_ok", torch.bool), ("errors", torch.int32), ("bad", torch.int32)):
+        _check_buf(getattr(out, name), "out." + name, dt, dev, F)
+    _capi.check(_capi.lib().lora_decode_batch(_ptr(s), F, S, _row_stride(s), _ptr(pay), _row_stride(pay),
+                                              out.crc_ok.data_ptr(), out.errors.data_ptr(), out.bad.data_ptr(),
+                                              dev.index, _stream(dev)))
+    return out
+
+
+def chain_symbols(sf: int, cr, nbytes: int) -> int:
+    """Symbols per frame of the chain for ``nbytes`` payload bytes (host arithmetic)."""
+    return _capi.check(_capi.lib().lora_chain_symbols(int(sf), codes.rdd_of(cr), int(nbytes)))
+
+
+def chain_capacity(sf: int, cr, nsymbols: int) -> int:
+    """Payload bytes ``nsymbols`` symbols carry through the chain (whole blocks only)."""
+    return min(MAX_PAYLOAD, nsymbols // (4 + codes.rdd_of(cr)) * int(sf) // 2)
+
+
+def encode_chain(payload: torch.Tensor, sf: int, cr, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """codes.encode_chain on the device: nibbles -> codewords of rate 4/(4+RDD) (zero
+    codewords pad to a multiple of sf) -> whitening -> diagonal interleave -> Gray.  ``cr``
+    as codes.rdd_of takes it ('4/5'..'4/8', or RDD 0..4).  Returns uint16 [F, S]."""
+    rdd = codes.rdd_of(cr)
+    p, squeeze = _rows(payload, "payload", torch.uint8)
+    F, n = p.shape
+    lib = _capi.lib()
+    S = _capi.check(lib.lora_chain_symbols(int(sf), rdd, n))
+    o = _out_rows(out, "out", torch.uint16, F, S, squeeze, p.device)
+    _capi.check(lib.lora_encode_chain_batch(int(sf), rdd, _ptr(p), F, n, _row_stride(p), _ptr(o), _row_stride(o),
+                                            p.device.index, _stream(p.device)))
+    return o[0] if squeeze else o
+
+
+def decode_chain(symbols: torch.Tensor, sf: int, cr, nbytes: int, out: Optional[DecodeResult] = None) -> DecodeResult:
+    """codes.decode_chain on the device: Gray -> diagonal deinterleave (whole blocks of 4+RDD
+    symbols; trailing symbols are ignored) -> de-whitening -> nibble decode -> ``nbytes``
+    bytes.  ``errors`` counts the codewords among the first 2 * nbytes that flagged an error;
+    ``crc_ok`` and ``bad`` are None."""
+    rdd = codes.rdd_of(cr)
+    s, squeeze = _symbols(symbols)
+    F, S = s.shape
+    nbytes = int(nbytes)
+    if not 0 <= nbytes <= MAX_PAYLOAD:
+        raise ValueError(f"nbytes must be in 0..{MAX_PAYLOAD}")
+    dev = s.device
+    if out is None:
+        out = DecodeResult(payload=torch.empty((nbytes,) if squeeze else (F, nbytes), dtype=torch.uint8,
+                                               device=dev),
+                           crc_ok=None, errors=torch.empty(F, dtype=torch.int32, device=dev), bad=None)
+    pay = _out_rows(out.payload, "out.payload", torch.uint8, F, nbytes, squeeze, dev)
+    _check_buf(out.errors, "out.errors", torch.int32, dev, F)
+    _capi.check(_capi.lib().lora_decode_chain_batch(int(sf), rdd, _ptr(s), F, S, _row_stride(s), nbytes, _ptr(pay),
+                                                    _row_stride(pay), out.errors.data_ptr(), dev.index,
+                                                    _stream(dev)))
+    return out

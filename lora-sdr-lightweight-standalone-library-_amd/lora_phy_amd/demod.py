@@ -259,6 +259,34 @@ class LoRaDemod:
         self.last = self.plan.run(iq)
         return self.last
 
+    def work_payload(self, iq: torch.Tensor, nbytes: Optional[int] = None, chain: str = "library"):
+        """Demodulate, then decode the symbols on the device (lora_phy_amd.codec): payload
+        bytes come out and nothing visits the host.  Returns a codec.DecodeResult; the
+        demodulator's own per-frame results are in ``last``.
+
+        ``chain="library"``: lora_decode with the CRC check of lora_phy::decode
+        (phy.cpp:241-256) over the first ``2 * nbytes`` symbols of each frame (default: all
+        of them).  ``chain="lora"``: the coding chain at this block's ``sf`` and ``cr``
+        (Gray, deinterleave, de-whitening, nibble decode) to ``nbytes`` bytes (default: as
+        many as the frame's whole blocks carry, at most 255)."""
+        from . import codec
+
+        if chain not in ("library", "lora"):
+            raise ValueError('chain must be "library" or "lora"')
+        self.last = self.plan.run(iq)
+        syms = self.last.symbols
+        if iq.dim() == 1:
+            syms = syms[0]
+        if chain == "lora":
+            if nbytes is None:
+                nbytes = codec.chain_capacity(self.sf, self.cr, syms.shape[-1])
+            return codec.decode_chain(syms, self.sf, self.cr, nbytes)
+        if nbytes is not None:
+            if not 0 <= 2 * int(nbytes) <= syms.shape[-1]:
+                raise ValueError(f"nbytes={nbytes} needs {2 * int(nbytes)} symbols, the frames have {syms.shape[-1]}")
+            syms = syms[..., :2 * int(nbytes)]
+        return codec.decode(syms)
+
     def sync_ok(self) -> torch.Tensor:
         """Per-frame flag: recovered sync word equals the configured one."""
         if self.last is None:

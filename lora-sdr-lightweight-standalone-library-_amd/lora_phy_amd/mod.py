@@ -46,8 +46,9 @@ class LoRaMod:
     (examples/lora_simulation.pth:312-326: sf, sync, padding, ampl, ovs) plus bw."""
 
     def __init__(self, sf: int, sync: int = 0x12, padding: int = 0, ampl: float = 1.0,
-                 ovs: int = 1, bw: int = 125000, device=None):
+                 ovs: int = 1, bw: int = 125000, device=None, cr=1):
         self.sf, self.sync, self.padding = int(sf), int(sync) & 0xFF, int(padding)
+        self.cr = cr  # coding rate of work_payload(chain="lora"), as codes.rdd_of takes it
         self.ampl, self.ovs, self.bw = float(ampl), int(ovs) if ovs else 1, int(bw)
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None
                                    else torch.device(device).index or 0)
@@ -61,3 +62,23 @@ class LoRaMod:
             pad = torch.zeros(iq.shape[:-1] + (self.padding,), dtype=iq.dtype, device=iq.device)
             iq = torch.cat([iq, pad], dim=-1)
         return iq
+
+    def work_payload(self, payload, chain: str = "library", append_crc: bool = False) -> torch.Tensor:
+        """Encode payload bytes ([F, n] or [n] uint8) on the device (lora_phy_amd.codec), then
+        modulate.  ``chain="library"``: lora_encode (LoRaEncoder.cpp:8-19), with
+        ``append_crc`` the SX1272 data checksum appended; ``chain="lora"``: the coding chain at
+        this block's ``sf`` and ``cr``."""
+        from . import codec
+
+        if chain not in ("library", "lora"):
+            raise ValueError('chain must be "library" or "lora"')
+        if chain == "lora" and append_crc:
+            raise ValueError('append_crc belongs to chain="library"')
+        if not isinstance(payload, torch.Tensor):
+            payload = torch.as_tensor(payload, dtype=torch.uint8)
+        payload = payload.to(self.device)
+        if chain == "lora":
+            symbols = codec.encode_chain(payload, self.sf, self.cr)
+        else:
+            symbols = codec.encode(payload, append_crc=append_crc)
+        return self.work(symbols)
