@@ -149,6 +149,47 @@ int64_t lora_compensate_offsets_batch(unsigned sf, unsigned osr, const float* in
                                       const float* time_offset, int device, void* stream,
                                       float* out);
 
+/* Per-symbol detector metrics: what LoRaDetector<float>::detect returns beside the index
+ * (LoRaDetector.hpp:39-74), which every reference caller receives (LoRaDemod.cpp:99-100,
+ * 163-164, phy.cpp:111-112,226-227) and lora_demod_batch drops.  Rows are `stride` elements
+ * apart; column s is whole symbol s of the frame, 0 <= s < total = frame_len / (N*osr): the
+ * sync symbols are columns 0 and 1 (no offset by 2 as in lora_demod_outputs.symbols).
+ * Device pointers; any pointer may be NULL. */
+typedef struct {
+  float* power;      /* [frames][stride] detect()'s power, dB   (LoRaDetector.hpp:64) */
+  float* power_avg;  /* [frames][stride] detect()'s powerAvg    (LoRaDetector.hpp:60-63) */
+  float* f_index;    /* [frames][stride] detect()'s fIndex      (LoRaDetector.hpp:66-71) */
+  uint16_t* index;   /* [frames][stride] detect()'s return value (LoRaDetector.hpp:73) */
+  int64_t stride;    /* elements between frames, >= symbols per frame */
+} lora_symbol_metrics;
+
+/* The detector's outputs for every whole symbol of `frames` frames laid out as for
+ * lora_demod_batch, on the FFT input the reference feeds for that symbol in the plan's mode:
+ *   LEGACY (LoRaDemod.cpp:137-164): t_off = (int)round(time_offset[f]), rate =
+ *     -2*pi*cfo[f]/N, the window base with the guards of :143-149, then per point the
+ *     caller-side dechirp (params.dechirp), the scale 1/max_amp[f] when max_amp[f] > 1
+ *     (:68-77), the cosf/sinf rotation (:151-158) and the window (:159-160);
+ *   API (phy.cpp:197-227): a fresh down-chirp's [i] per symbol, the same rotation and base
+ *     rule, no normalisation (max_amp is ignored and may be NULL);
+ *   RAW: (dechirp) -> window -> detect; cfo, time_offset and max_amp are ignored and may be
+ *     NULL.
+ * cfo / time_offset / max_amp are device arrays of `frames` floats: the values
+ * lora_demod_batch wrote for the same frames.  Any float is accepted: the conversion of
+ * time_offset saturates (NaN gives 0) and the base guards keep every window in its frame.
+ * The arithmetic is always the exact one (bit-identical to detect(), including the double
+ * total taken in bin order, :45-52), whatever precision and pipeline the plan was made with.
+ * Enqueues one kernel on `stream`, allocates and synchronises nothing, needs no workspace,
+ * and fully writes columns 0 .. total-1 of every output given and nothing beyond them.
+ * frames == 0, total == 0 or all four outputs NULL: no launch.  LORA_EINVAL, before any HIP
+ * call: a NULL plan, out or iq (frames > 0), negative sizes, frame_len >= 2^31, frame_stride <
+ * frame_len with more than one frame, stride < total with an output given, a NULL cfo /
+ * time_offset / max_amp in LEGACY, a NULL cfo / time_offset in API; in API mode frame_len
+ * must satisfy lora_demod_symbols_per_frame (phy.cpp:186-188).  Returns total. */
+int64_t lora_demod_metrics_batch(lora_demod_plan* plan, const float* iq, int64_t frames,
+                                 int64_t frame_len, int64_t frame_stride, const float* cfo,
+                                 const float* time_offset, const float* max_amp,
+                                 const lora_symbol_metrics* out, void* stream);
+
 /* lora_modulate for `frames` independent frames: symbols [frames][sym_count] ->
  * iq [frames][(sym_count+2)*N*osr] (2 sync up-chirps then one chirp per symbol,
  * phase-continuous within a frame, LoRaMod.cpp:8-41).  Returns samples per frame. */

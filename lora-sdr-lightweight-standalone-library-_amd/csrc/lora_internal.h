@@ -3,6 +3,7 @@
 #include <complex>
 #include <string>
 
+#include "../../include/lora_mi355x.h"
 #include "lora_device.h"
 
 namespace lora {
@@ -126,6 +127,14 @@ bool launch_spec(const KArgs& a, int64_t frames, int stage, hipStream_t st);
 // Offset estimate + sync symbols with the same FFT machinery, one lane group per frame
 // (frames with >= 2 whole symbols; false = not covered, use k_estimate).
 bool launch_est_fast(const KArgs& a, int64_t frames, hipStream_t st);
+
+// Per-symbol detector metrics (lora_metrics.hip, k_detect_metrics): every whole symbol
+// (a.total per frame, sync symbols included) of `frames` frames, the window built from the
+// per-frame device arrays cfo / toff / max_amp in a.mode's way, always with the exact
+// arithmetic.  Uses a's frame geometry, mode flags and plan tables only (no workspace, no
+// FrameParams).  Returns LORA_OK or a negative error with the last-error text set.
+int launch_detect_metrics(const KArgs& a, const float* cfo, const float* toff, const float* max_amp,
+                          const lora_symbol_metrics& o, int64_t frames, hipStream_t st);
 
 // ---- launch recording: the C++ drop-in's allocation-free dispatch (lora_aql.hip) -------
 // Every kernel launch of lora_demod_batch goes through lora::launch.  Normally that is

@@ -9,10 +9,10 @@ phy.hpp-style functional API is in :mod:`lora_phy_amd.phy`.
 """
 from . import _capi, codec, codes, iq_io, phy, shard  # noqa: F401
 from ._capi import LoraError
-from .demod import DemodPlan, DemodResult, LoRaDemod, compensate_offsets, spec_pipeline
+from .demod import DemodPlan, DemodResult, DetectMetrics, LoRaDemod, compensate_offsets, spec_pipeline
 from .mod import LoRaMod, modulate
 
-__all__ = ["DemodPlan", "DemodResult", "LoRaDemod", "LoRaMod", "LoraError", "modulate",
+__all__ = ["DemodPlan", "DemodResult", "DetectMetrics", "LoRaDemod", "LoRaMod", "LoraError", "modulate",
            "compensate_offsets", "spec_pipeline", "codec", "codes", "iq_io", "phy", "shard", "lib_path", "version", "source_hash",
            "check_build"]
 

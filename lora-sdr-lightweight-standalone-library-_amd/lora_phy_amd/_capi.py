@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "lora_demod_symbols_per_frame",
     "lora_demod_workspace_bytes",
     "lora_demod_batch",
+    "lora_demod_metrics_batch",
     "lora_mod_batch",
     "lora_estimate_offsets_batch",
     "lora_compensate_offsets_batch",
@@ -78,6 +79,18 @@ class DemodOutputs(C.Structure):
     ]
 
 
+class SymbolMetrics(C.Structure):
+    """lora_symbol_metrics: the detector's per-symbol outputs (any pointer may be NULL)."""
+
+    _fields_ = [
+        ("power", C.c_void_p),
+        ("power_avg", C.c_void_p),
+        ("f_index", C.c_void_p),
+        ("index", C.c_void_p),
+        ("stride", C.c_int64),
+    ]
+
+
 class LoraError(RuntimeError):
     """Raised for negative return codes of the C-ABI (reference: -1 / 0 returns)."""
 
@@ -110,6 +123,10 @@ def lib() -> C.CDLL:
     L.lora_demod_batch.restype = C.c_int64
     L.lora_demod_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                    C.POINTER(DemodOutputs), C.c_void_p, C.c_size_t, C.c_void_p]
+    L.lora_demod_metrics_batch.restype = C.c_int64
+    L.lora_demod_metrics_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SymbolMetrics),
+                                           C.c_void_p]
     L.lora_mod_batch.restype = C.c_int64
     L.lora_mod_batch.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_float, C.c_uint8, C.c_void_p,
                                  C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]

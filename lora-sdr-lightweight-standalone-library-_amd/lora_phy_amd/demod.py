@@ -36,6 +36,32 @@ class DemodResult:
     max_amp: torch.Tensor      # [F] float32     (LoRaDemod.cpp:59-67; 0 in API mode)
 
 
+@dataclass
+class DetectMetrics:
+    """What LoRaDetector::detect returns for every whole symbol of every frame
+    (LoRaDetector.hpp:39-74), column s = symbol s of the frame: the sync symbols are
+    columns 0 and 1 and ``DemodResult.symbols`` equals ``index[:, 2:]``.  All tensors are on
+    the plan's device; a field is None only where the caller's ``out=`` left it out."""
+
+    power: Optional[torch.Tensor]      # [F, total] float32  the peak bin, dB          (:64)
+    power_avg: Optional[torch.Tensor]  # [F, total] float32  every other bin, dB       (:60-63)
+    f_index: Optional[torch.Tensor]    # [F, total] float32  fractional-bin offset     (:66-71)
+    index: Optional[torch.Tensor]      # [F, total] uint16   the argmax bin            (:73)
+
+    @property
+    def snr_db(self) -> torch.Tensor:
+        """``power - power_avg`` per symbol, a plain torch subtraction: the peak over
+        everything else in the spectrum.  +inf where the floor is -inf (a noiseless tone on
+        an exact bin); NaN for an all-zero window (both are -inf)."""
+        return self.power - self.power_avg
+
+    def frame_snr_db(self, first: int = 2) -> torch.Tensor:
+        """Per frame, the mean of ``snr_db[:, first:]`` (default: the data symbols) - plain
+        torch ops, accumulated in float64 and returned as float32.  NaN for a frame with no
+        such symbol."""
+        return self.snr_db[:, first:].double().mean(dim=1).float()
+
+
 def _stream_handle(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -186,6 +212,61 @@ class DemodPlan:
                                                ws.data_ptr(), ws.numel(), _stream_handle(dev)))
         return out
 
+    def detect_metrics(self, iq: torch.Tensor, result: Optional[DemodResult] = None,
+                       out: Optional[DetectMetrics] = None) -> DetectMetrics:
+        """The detector's per-symbol outputs (lora_demod_metrics_batch) for the frames of a
+        [F, L] (or [L]) complex64 CUDA tensor, laid out as for ``run``.
+
+        ``result``: the ``DemodResult`` of ``run`` on the same frames - its cfo, time_offset
+        and (legacy) max_amp rebuild each symbol's window; required for legacy / api plans,
+        ignored for raw ones.  ``out``: a ``DetectMetrics`` whose tensors ([>= F, >= total],
+        unit column stride, one common row stride) receive columns 0 .. total-1; a field left
+        None is not computed.  One kernel on the current stream, nothing allocated besides the
+        outputs, so the call can be captured in a HIP graph."""
+        iq = _check_iq(iq, self.device)
+        F, L = iq.shape
+        dev = self.device
+        if self.mode == "api":
+            self.symbols_per_frame(L)  # the plan's frame-length rule
+        total = L // self.step
+        cfo = toff = amp = None
+        if self.mode != "raw":
+            if result is None:
+                raise ValueError(f"a {self.mode} plan needs result= (the DemodResult of run() on these frames)")
+            names = ("cfo", "time_offset") + (("max_amp",) if self.mode == "legacy" else ())
+            for name in names:
+                _check_buf(getattr(result, name), "result." + name, torch.float32, dev, F)
+            cfo, toff = result.cfo.data_ptr(), result.time_offset.data_ptr()
+            amp = result.max_amp.data_ptr() if self.mode == "legacy" else None
+        if out is None:
+            out = DetectMetrics(*(torch.empty((F, total), dtype=dt, device=dev)
+                                  for dt in (torch.float32, torch.float32, torch.float32, torch.uint16)))
+        given = []
+        for name, dt in (("power", torch.float32), ("power_avg", torch.float32), ("f_index", torch.float32),
+                         ("index", torch.uint16)):
+            t = getattr(out, name)
+            if t is None:
+                continue
+            _require_cuda(t, "out." + name)
+            if t.dtype != dt:
+                raise TypeError(f"out.{name} must be {dt}, got {t.dtype}")
+            if (t.device != dev or t.dim() != 2 or t.shape[0] < F or t.shape[1] < total
+                    or (t.shape[1] > 1 and t.stride(1) != 1) or (F > 1 and t.stride(0) < total)):
+                raise ValueError(f"out.{name} must be a {dt} [>={F}, >={total}] tensor on {dev} with unit "
+                                 "column stride and non-overlapping rows")
+            given.append(t)
+        # one row stride for the four outputs (lora_symbol_metrics.stride); a single frame has none
+        strides = {t.stride(0) for t in given} if F > 1 else set()
+        if len(strides) > 1:
+            raise ValueError("the tensors of out must share one row stride")
+        m = _capi.SymbolMetrics(*(getattr(out, n).data_ptr() if getattr(out, n) is not None else None
+                                  for n in ("power", "power_avg", "f_index", "index")),
+                                strides.pop() if strides else total)
+        stride = iq.stride(0) if F > 1 else L
+        _capi.check(self._lib.lora_demod_metrics_batch(self._h, iq.data_ptr(), F, L, stride, cfo, toff, amp,
+                                                       C.byref(m), _stream_handle(dev)))
+        return out
+
     def estimate_offsets(self, iq: torch.Tensor, cfo: torch.Tensor, time_offset: torch.Tensor) -> int:
         """phy.cpp:78-145 over every whole symbol of each frame (raw samples)."""
         iq = _check_iq(iq, self.device)
@@ -231,7 +312,9 @@ class LoRaDemod:
       * ``thresh`` - a detection threshold in dB.  The reference library path
         (LoRaDemod.cpp:49-195) has no detection gate, so no gate is applied; only the
         graph's value -30.0 (examples/lora_simulation.pth:440) is accepted, and any
-        other value raises instead of being silently ignored.
+        other value raises instead of being silently ignored.  The values such a gate would
+        compare - the detector's per-symbol power and noise floor - come from
+        ``work_metrics``; what to do with them is the caller's decision.
     """
 
     THRESH_DEFAULT = -30.0
@@ -286,6 +369,14 @@ class LoRaDemod:
                 raise ValueError(f"nbytes={nbytes} needs {2 * int(nbytes)} symbols, the frames have {syms.shape[-1]}")
             syms = syms[..., :2 * int(nbytes)]
         return codec.decode(syms)
+
+    def work_metrics(self, iq: torch.Tensor) -> DetectMetrics:
+        """Demodulate (``last`` is set as by ``work_frames``), then return the detector's
+        per-symbol power, noise floor and fractional index for the same frames
+        (``DemodPlan.detect_metrics``): the link quality behind ``last.symbols``.  No gate
+        acts on them (see ``thresh``)."""
+        self.last = self.plan.run(iq)
+        return self.plan.detect_metrics(iq, self.last)
 
     def sync_ok(self) -> torch.Tensor:
         """Per-frame flag: recovered sync word equals the configured one."""
