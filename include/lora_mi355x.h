@@ -190,6 +190,33 @@ int64_t lora_demod_metrics_batch(lora_demod_plan* plan, const float* iq, int64_t
                                  const float* time_offset, const float* max_amp,
                                  const lora_symbol_metrics* out, void* stream);
 
+/* Sliding detector scan of continuous streams: LoRaDetector<float>::detect
+ * (LoRaDetector.hpp:39-74) on a window of step = N*osr samples that starts every `hop` samples
+ * of each of `rows` rows of `row_len` complex samples (row r at iq + 2*r*row_stride floats).
+ * Window w of a row starts at sample w*hop; a row has
+ *   W = row_len < step ? 0 : (row_len - step) / hop + 1
+ * of them and none reads past row_len.  The FFT input of a window is what a LORA_MODE_RAW plan
+ * feeds for a one-symbol frame cut at that sample: point i is x[w*hop + i*osr], times
+ * down[i*osr] (the table index counts from the window start) when params.dechirp is set, times
+ * the window table for LORA_WINDOW_HANN; no normalisation, estimate or rotation.  Every output
+ * is bit-identical to what lora_demod_metrics_batch returns in LORA_MODE_RAW for the same
+ * N*osr samples given as one frame (the exact arithmetic, including the double total taken in
+ * bin order, LoRaDetector.hpp:45-52).  The outputs are lora_symbol_metrics' four, laid out
+ * [rows][stride] with column w.  Uses the plan's sf, osr, bw, window and dechirp only; the mode
+ * is ignored, as in lora_estimate_offsets_batch.  Any hop >= 1 is legal (odd, or > step).
+ *
+ * lora_detect_scan_windows: host arithmetic only; W, or LORA_EINVAL for a NULL plan, a
+ * negative row_len or hop < 1.
+ * lora_detect_scan_batch: enqueues one kernel on `stream`, allocates and synchronises nothing,
+ * needs no workspace, and fully writes columns 0 .. W-1 of every output given and nothing
+ * beyond them.  rows == 0, W == 0 or all four outputs NULL: no launch.  LORA_EINVAL, before
+ * any HIP call: a NULL plan or out, a NULL iq with work to do, negative sizes, hop < 1,
+ * row_len >= 2^31, row_stride < row_len with more than one row, out->stride < W with an
+ * output given, a grid beyond 2^31 (rows * ceil(W / windows per workgroup)).  Returns W. */
+int64_t lora_detect_scan_windows(const lora_demod_plan* plan, int64_t row_len, int64_t hop);
+int64_t lora_detect_scan_batch(lora_demod_plan* plan, const float* iq, int64_t rows, int64_t row_len,
+                               int64_t row_stride, int64_t hop, const lora_symbol_metrics* out, void* stream);
+
 /* lora_modulate for `frames` independent frames: symbols [frames][sym_count] ->
  * iq [frames][(sym_count+2)*N*osr] (2 sync up-chirps then one chirp per symbol,
  * phase-continuous within a frame, LoRaMod.cpp:8-41).  Returns samples per frame. */

@@ -1787,6 +1787,53 @@ int64_t lora_demod_metrics_batch(lora_demod_plan* plan, const float* iq, int64_t
   return rc < 0 ? rc : total;
 }
 
+int64_t lora_detect_scan_windows(const lora_demod_plan* plan, int64_t row_len, int64_t hop) {
+  if (!plan) return set_error(LORA_EINVAL, "null plan");
+  if (row_len < 0 || hop < 1) return set_error(LORA_EINVAL, "row_len must be >= 0 and hop >= 1");
+  return lora::scan_windows(row_len, plan->step, hop);
+}
+
+int64_t lora_detect_scan_batch(lora_demod_plan* plan, const float* iq, int64_t rows, int64_t row_len,
+                               int64_t row_stride, int64_t hop, const lora_symbol_metrics* out, void* stream) {
+  if (!plan || !out) return set_error(LORA_EINVAL, "null argument");
+  if (rows < 0 || row_len < 0 || row_stride < 0 || out->stride < 0)
+    return set_error(LORA_EINVAL, "negative rows / row_len / row_stride / stride");
+  if (hop < 1) return set_error(LORA_EINVAL, "hop must be >= 1");
+  if (row_len >= (int64_t(1) << 31)) return set_error(LORA_EINVAL, "row_len must be < 2^31");
+  if (rows > 1 && row_stride < row_len) return set_error(LORA_EINVAL, "row_stride smaller than row_len");
+  const int64_t W = lora::scan_windows(row_len, plan->step, hop);
+  const bool any = out->power || out->power_avg || out->f_index || out->index;
+  if (any && out->stride < W) return set_error(LORA_EINVAL, "stride smaller than windows per row");
+  const lora_demod_params& p = plan->prm;
+  const int64_t grid = lora::scan_grid((int)p.sf, W, rows);
+  if (grid < 0) return set_error(LORA_EINVAL, "batch too large");
+  if (grid > 0 && !iq) return set_error(LORA_EINVAL, "null iq");
+  if (grid == 0 || !any) return W;
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  if (prev != p.device) HIP_TRY(hipSetDevice(p.device));
+  KArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.iq = reinterpret_cast<const cf*>(iq);
+  a.frame_len = row_len;
+  a.frame_stride = row_stride;
+  a.sf = (int)p.sf;
+  a.N = plan->N;
+  a.osr = (int)p.osr;
+  a.step = plan->step;
+  a.mode = LORA_MODE_RAW;
+  a.dechirp = p.dechirp ? 1 : 0;
+  a.hann = p.window == LORA_WINDOW_HANN;
+  a.power_scale = plan->power_scale;
+  a.tw = plan->tw;
+  a.rev = plan->rev;
+  a.win = plan->win;
+  a.down = plan->down;
+  const int rc = lora::launch_detect_scan(a, *out, rows, hop, static_cast<hipStream_t>(stream));
+  if (prev != p.device) hipSetDevice(prev);
+  return rc < 0 ? rc : W;
+}
+
 int64_t lora_compensate_offsets_batch(unsigned sf, unsigned osr, const float* in, int64_t frames,
                                       int64_t frame_len, int64_t frame_stride, const float* cfo,
                                       const float* time_offset, int device, void* stream,

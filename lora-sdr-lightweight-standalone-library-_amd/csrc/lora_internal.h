@@ -136,6 +136,22 @@ bool launch_est_fast(const KArgs& a, int64_t frames, hipStream_t st);
 int launch_detect_metrics(const KArgs& a, const float* cfo, const float* toff, const float* max_amp,
                           const lora_symbol_metrics& o, int64_t frames, hipStream_t st);
 
+// Symbols (windows) per workgroup of the detector-metrics kernels (k_detect_metrics,
+// k_detect_scan): G * N = 4096 points (32 KiB of spectra + 16 KiB of |X|^2), at most one
+// wave's worth of symbols, since the ordered sums take one lane per symbol.
+__host__ __device__ constexpr int metrics_group(int sf) { return sf >= 6 ? 4096 >> sf : 64; }
+
+// Sliding detector scan (lora_scan.hip, k_detect_scan).  scan_windows: windows per row, one
+// every `hop` samples while a whole one (`step` samples) fits.  scan_grid: workgroups for
+// `rows` rows of W windows, 0 when there is nothing to do, -1 beyond 2^31 - 1 (host
+// arithmetic, no HIP call).  launch_detect_scan: the detector's outputs for every window of
+// `rows` rows of a.frame_len samples, a.frame_stride apart, at o's [row * stride + w]; uses a's
+// sf / N / osr / step / dechirp / hann and plan tables only.  The caller has checked
+// scan_grid > 0.  Returns LORA_OK or a negative error with the last-error text set.
+int64_t scan_windows(int64_t row_len, int64_t step, int64_t hop);
+int64_t scan_grid(int sf, int64_t W, int64_t rows);
+int launch_detect_scan(const KArgs& a, const lora_symbol_metrics& o, int64_t rows, int64_t hop, hipStream_t st);
+
 // ---- launch recording: the C++ drop-in's allocation-free dispatch (lora_aql.hip) -------
 // Every kernel launch of lora_demod_batch goes through lora::launch.  Normally that is
 // hipLaunchKernelGGL; while a thread has a LaunchRecord installed (t_launch_record) the

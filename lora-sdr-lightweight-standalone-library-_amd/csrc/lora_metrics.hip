@@ -32,9 +32,6 @@ namespace lora {
 namespace {
 
 constexpr int kThreads = 256;
-// Symbols per workgroup: G * N = 4096 points (32 KiB of spectra + 16 KiB of |X|^2), at most
-// one wave's worth of symbols, since the ordered sums take one lane per symbol.
-__host__ __device__ constexpr int metrics_group(int sf) { return sf >= 6 ? 4096 >> sf : 64; }
 
 // Window base of symbol s with the t_off rule (LoRaDemod.cpp:142-149, phy.cpp:205-212):
 // lora_demod_fast.hip's sym_base, without the dechirp-table phase (the table index is taken

@@ -5,15 +5,16 @@ for gfx950).  IQ lives in torch.complex64 CUDA(HIP) tensors; the kernels run on 
 current torch stream.  Host-side coding helpers (Hamming, Gray, interleave,
 whitening, CRC) are in :mod:`lora_phy_amd.codes`, their batched device counterparts
 (symbols <-> payload bytes, one kernel per call) in :mod:`lora_phy_amd.codec`; the
-phy.hpp-style functional API is in :mod:`lora_phy_amd.phy`.
+phy.hpp-style functional API is in :mod:`lora_phy_amd.phy`; receiving a continuous stream
+(sliding detector scan, frame finder) is in :mod:`lora_phy_amd.stream`.
 """
-from . import _capi, codec, codes, iq_io, phy, shard  # noqa: F401
+from . import _capi, codec, codes, iq_io, phy, shard, stream  # noqa: F401
 from ._capi import LoraError
 from .demod import DemodPlan, DemodResult, DetectMetrics, LoRaDemod, compensate_offsets, spec_pipeline
 from .mod import LoRaMod, modulate
 
 __all__ = ["DemodPlan", "DemodResult", "DetectMetrics", "LoRaDemod", "LoRaMod", "LoraError", "modulate",
-           "compensate_offsets", "spec_pipeline", "codec", "codes", "iq_io", "phy", "shard", "lib_path", "version", "source_hash",
+           "compensate_offsets", "spec_pipeline", "codec", "codes", "iq_io", "phy", "shard", "stream", "lib_path", "version", "source_hash",
            "check_build"]
 
 

@@ -36,6 +36,8 @@ EXPORTED_SYMBOLS = (
     "lora_demod_workspace_bytes",
     "lora_demod_batch",
     "lora_demod_metrics_batch",
+    "lora_detect_scan_windows",
+    "lora_detect_scan_batch",
     "lora_mod_batch",
     "lora_estimate_offsets_batch",
     "lora_compensate_offsets_batch",
@@ -127,6 +129,11 @@ def lib() -> C.CDLL:
     L.lora_demod_metrics_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SymbolMetrics),
                                            C.c_void_p]
+    L.lora_detect_scan_windows.restype = C.c_int64
+    L.lora_detect_scan_windows.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
+    L.lora_detect_scan_batch.restype = C.c_int64
+    L.lora_detect_scan_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                         C.POINTER(SymbolMetrics), C.c_void_p]
     L.lora_mod_batch.restype = C.c_int64
     L.lora_mod_batch.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_float, C.c_uint8, C.c_void_p,
                                  C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]

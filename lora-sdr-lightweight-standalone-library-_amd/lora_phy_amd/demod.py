@@ -98,6 +98,37 @@ def _check_iq(iq: torch.Tensor, device: torch.device) -> torch.Tensor:
     return iq
 
 
+def _metric_outputs(out: Optional[DetectMetrics], F: int, total: int, dev: torch.device):
+    """The (DetectMetrics, lora_symbol_metrics) pair of a call that writes [F, total] values:
+    fresh tensors when ``out`` is None, else ``out``'s own after the checks the C library cannot
+    make on raw pointers."""
+    if out is None:
+        out = DetectMetrics(*(torch.empty((F, total), dtype=dt, device=dev)
+                              for dt in (torch.float32, torch.float32, torch.float32, torch.uint16)))
+    given = []
+    for name, dt in (("power", torch.float32), ("power_avg", torch.float32), ("f_index", torch.float32),
+                     ("index", torch.uint16)):
+        t = getattr(out, name)
+        if t is None:
+            continue
+        _require_cuda(t, "out." + name)
+        if t.dtype != dt:
+            raise TypeError(f"out.{name} must be {dt}, got {t.dtype}")
+        if (t.device != dev or t.dim() != 2 or t.shape[0] < F or t.shape[1] < total
+                or (t.shape[1] > 1 and t.stride(1) != 1) or (F > 1 and t.stride(0) < total)):
+            raise ValueError(f"out.{name} must be a {dt} [>={F}, >={total}] tensor on {dev} with unit "
+                             "column stride and non-overlapping rows")
+        given.append(t)
+    # one row stride for the four outputs (lora_symbol_metrics.stride); a single row has none
+    strides = {t.stride(0) for t in given} if F > 1 else set()
+    if len(strides) > 1:
+        raise ValueError("the tensors of out must share one row stride")
+    m = _capi.SymbolMetrics(*(getattr(out, n).data_ptr() if getattr(out, n) is not None else None
+                              for n in ("power", "power_avg", "f_index", "index")),
+                            strides.pop() if strides else total)
+    return out, m
+
+
 class DemodPlan:
     """A device plan for one demodulator configuration (lora_demod_init equivalent)."""
 
@@ -238,33 +269,38 @@ class DemodPlan:
                 _check_buf(getattr(result, name), "result." + name, torch.float32, dev, F)
             cfo, toff = result.cfo.data_ptr(), result.time_offset.data_ptr()
             amp = result.max_amp.data_ptr() if self.mode == "legacy" else None
-        if out is None:
-            out = DetectMetrics(*(torch.empty((F, total), dtype=dt, device=dev)
-                                  for dt in (torch.float32, torch.float32, torch.float32, torch.uint16)))
-        given = []
-        for name, dt in (("power", torch.float32), ("power_avg", torch.float32), ("f_index", torch.float32),
-                         ("index", torch.uint16)):
-            t = getattr(out, name)
-            if t is None:
-                continue
-            _require_cuda(t, "out." + name)
-            if t.dtype != dt:
-                raise TypeError(f"out.{name} must be {dt}, got {t.dtype}")
-            if (t.device != dev or t.dim() != 2 or t.shape[0] < F or t.shape[1] < total
-                    or (t.shape[1] > 1 and t.stride(1) != 1) or (F > 1 and t.stride(0) < total)):
-                raise ValueError(f"out.{name} must be a {dt} [>={F}, >={total}] tensor on {dev} with unit "
-                                 "column stride and non-overlapping rows")
-            given.append(t)
-        # one row stride for the four outputs (lora_symbol_metrics.stride); a single frame has none
-        strides = {t.stride(0) for t in given} if F > 1 else set()
-        if len(strides) > 1:
-            raise ValueError("the tensors of out must share one row stride")
-        m = _capi.SymbolMetrics(*(getattr(out, n).data_ptr() if getattr(out, n) is not None else None
-                                  for n in ("power", "power_avg", "f_index", "index")),
-                                strides.pop() if strides else total)
+        out, m = _metric_outputs(out, F, total, dev)
         stride = iq.stride(0) if F > 1 else L
         _capi.check(self._lib.lora_demod_metrics_batch(self._h, iq.data_ptr(), F, L, stride, cfo, toff, amp,
                                                        C.byref(m), _stream_handle(dev)))
+        return out
+
+    def scan_windows(self, row_len: int, hop: int) -> int:
+        """Windows ``scan`` computes per row of ``row_len`` samples: one every ``hop`` samples
+        while a whole one (``step``) fits, ``0 if row_len < step else (row_len - step) // hop + 1``
+        (lora_detect_scan_windows)."""
+        return _capi.check(self._lib.lora_detect_scan_windows(self._h, int(row_len), int(hop)))
+
+    def scan(self, iq: torch.Tensor, hop: int, out: Optional[DetectMetrics] = None) -> DetectMetrics:
+        """The sliding detector scan (lora_detect_scan_batch) of continuous streams: a [L] or
+        [R, L] complex64 CUDA tensor, one stream per row (rows may be a strided view with
+        non-overlapping rows).  Column w of the [R, W] result is the detector on the ``step``
+        samples from ``w * hop``, bit-identical to ``detect_metrics`` of a raw plan on those
+        samples as one frame: the plan's dechirp and window apply, its mode does not.  Any
+        ``hop >= 1``; ``W = scan_windows(L, hop)``.  ``out`` follows ``detect_metrics``' rules
+        with W for total.  One kernel on the current stream, nothing allocated besides the
+        outputs, so the call can be captured in a HIP graph."""
+        iq = _check_iq(iq, self.device)
+        R, L = iq.shape
+        hop = int(hop)
+        if hop < 1:
+            raise ValueError("hop must be >= 1")
+        W = 0 if L < self.step else (L - self.step) // hop + 1
+        out, m = _metric_outputs(out, R, W, self.device)
+        stride = iq.stride(0) if R > 1 else L
+        got = _capi.check(self._lib.lora_detect_scan_batch(self._h, iq.data_ptr(), R, L, stride, hop, C.byref(m),
+                                                           _stream_handle(self.device)))
+        assert got == W, (got, W)
         return out
 
     def estimate_offsets(self, iq: torch.Tensor, cfo: torch.Tensor, time_offset: torch.Tensor) -> int:
@@ -377,6 +413,20 @@ class LoRaDemod:
         acts on them (see ``thresh``)."""
         self.last = self.plan.run(iq)
         return self.plan.detect_metrics(iq, self.last)
+
+    def work_stream(self, iq: torch.Tensor, frame_symbols: int, hop: Optional[int] = None,
+                    thresh_db: float = 0.0):
+        """Receive a continuous [L] stream (``lora_phy_amd.stream.receive`` with this block's plan
+        and sync word): scan, find the frames of ``frame_symbols`` data symbols, cut them out and
+        demodulate them.  Returns ``(starts, symbols[:, :mtu])`` - the int64 [K] sample index of
+        each frame's first sync symbol and its data symbols; ``last`` keeps the DemodResult of
+        the K frames.  ``thresh_db`` gates ``power - power_avg`` of both sync windows and has
+        nothing to do with ``thresh``, which stays as it is."""
+        from . import stream
+
+        starts, res = stream.receive(self.plan, iq, frame_symbols, hop, self.sync, thresh_db)
+        self.last = res
+        return starts, res.symbols[:, :self.mtu]
 
     def sync_ok(self) -> torch.Tensor:
         """Per-frame flag: recovered sync word equals the configured one."""

@@ -8,7 +8,7 @@ host RAM stream through; frames are rows of `frame_len` samples.
 from __future__ import annotations
 
 import os
-from typing import Iterator, Optional
+from typing import Iterator, Optional, Tuple
 
 import numpy as np
 import torch
@@ -47,6 +47,30 @@ def iter_frames(path: str, frame_len: int, frames_per_chunk: int, device=None) -
         n = min(frames_per_chunk, nf - f0)
         host = np.array(x[f0 * frame_len:(f0 + n) * frame_len]).reshape(n, frame_len)
         yield torch.from_numpy(host).to(dev)
+
+
+def iter_stream(path: str, chunk_samples: int, overlap: int, device=None) -> Iterator[Tuple[int, torch.Tensor]]:
+    """Stream a capture as overlapping 1-D chunks: yields ``(offset, tensor)`` with
+    ``tensor = file[offset : offset + chunk_samples + overlap]`` on ``device`` for offset = 0,
+    chunk_samples, 2 * chunk_samples, ... while offset is inside the file.  Consecutive chunks
+    share ``overlap`` samples; the last chunk, and only it, holds at most ``chunk_samples``.
+
+    Receiving a continuous recording larger than HBM (``lora_phy_amd.stream``), with frames of
+    ``frame_len = (frame_symbols + 2) * step`` samples: choose ``overlap >= frame_len + step``,
+    so that a frame starting anywhere before ``chunk_samples`` lies whole in its chunk together
+    with the windows that find it.  Per chunk, scan it and call ``find_frames`` with
+    ``first = max(0, end_of_last_accepted_frame - offset)`` and ``row_len = len(tensor)``; in
+    every chunk but the last, leave the starts at or beyond ``chunk_samples`` to the next
+    chunk, which sees them again at ``start - chunk_samples``.  A frame's position in the file
+    is ``offset + start`` and it ends at ``offset + start + frame_len``: every frame is found
+    exactly once, whichever side of a chunk border it begins on."""
+    chunk_samples, overlap = int(chunk_samples), int(overlap)
+    if chunk_samples < 1 or overlap < 0:
+        raise ValueError("chunk_samples must be >= 1 and overlap >= 0")
+    x = _mmap(path)
+    dev = torch.device("cpu") if device is None else torch.device(device)
+    for off in range(0, len(x), chunk_samples):
+        yield off, torch.from_numpy(np.array(x[off:off + chunk_samples + overlap])).to(dev)
 
 
 def write_iq(path: str, iq: torch.Tensor) -> int:
