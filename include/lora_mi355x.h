@@ -190,6 +190,34 @@ int64_t lora_demod_metrics_batch(lora_demod_plan* plan, const float* iq, int64_t
                                  const float* time_offset, const float* max_amp,
                                  const lora_symbol_metrics* out, void* stream);
 
+/* Soft bits per symbol: a max-log LLR for each of the sf bits a symbol carries, from the same
+ * spectrum lora_demod_metrics_batch reduces to one index.  Frames, cfo / time_offset / max_amp
+ * and the FFT input of every whole symbol are exactly those of lora_demod_metrics_batch
+ * (LoRaDemod.cpp:137-164, phy.cpp:197-227, or the bare detector in LORA_MODE_RAW), with the
+ * exact arithmetic whatever precision and pipeline the plan was made with.  Column s is whole
+ * symbol s, 0 <= s < total = frame_len / (N*osr); the sync symbols are columns 0 and 1.
+ * llr is [frames][llr_stride][sf] floats, llr_stride in symbols: bit c of symbol s of frame f
+ * is llr[(f * llr_stride + s) * sf + c].  For one symbol with spectrum X:
+ *   P[k] = re*re + im*im in fp32, no contraction (LoRaDetector.hpp:51);
+ *   Q[k] = P[k] > 0 ? P[k] : 0 (the detector's strict '>', :53-57: NaN and 0 never win);
+ *   v(k) = grayToBinary16(k), the value the chain deinterleaves (LoRaCodes.hpp:212-222);
+ *   m1 = max{Q[k] : bit c of v(k) = 1}, m0 = max{Q[k] : bit c of v(k) = 0};
+ *   llr[c] = (m1 == m0) ? +0.0f : m1 - m0, one fp32 subtraction.
+ * Positive means the bit is 1; wherever llr[c] != 0 its sign is bit c of grayToBinary16 of the
+ * detector's index.  A silent window and inf - inf give +0.0f, so no NaN is ever written.  The
+ * values are not normalised by the noise floor (lora_decode_chain_soft_batch is scale-free;
+ * power_avg of lora_demod_metrics_batch is the floor).  The detector's double total is not
+ * computed.  This definition is the library's own: the reference has no soft path.
+ * Enqueues one kernel on `stream`, allocates and synchronises nothing, needs no workspace, and
+ * fully writes columns 0 .. total-1 of every row and nothing beyond them.  frames == 0,
+ * total == 0 or a NULL llr: no launch.  LORA_EINVAL, before any HIP call: everything
+ * lora_demod_metrics_batch refuses, llr_stride < total, and a plan with sf < 6 (the chain that
+ * consumes the bits is defined for SF 6-12).  Returns total. */
+int64_t lora_demod_soft_bits_batch(lora_demod_plan* plan, const float* iq, int64_t frames,
+                                   int64_t frame_len, int64_t frame_stride, const float* cfo,
+                                   const float* time_offset, const float* max_amp,
+                                   float* llr, int64_t llr_stride, void* stream);
+
 /* Sliding detector scan of continuous streams: LoRaDetector<float>::detect
  * (LoRaDetector.hpp:39-74) on a window of step = N*osr samples that starts every `hop` samples
  * of each of `rows` rows of `row_len` complex samples (row r at iq + 2*r*row_stride floats).
@@ -267,6 +295,30 @@ int64_t lora_encode_batch(const uint8_t* payload, int64_t frames, int64_t nbytes
 int64_t lora_decode_chain_batch(int sf, int rdd, const uint16_t* symbols, int64_t frames, int64_t sym_count,
                                 int64_t sym_stride, int64_t nbytes, uint8_t* payload, int64_t payload_stride,
                                 int32_t* err_count, int device, void* stream);
+
+/* lora_decode_chain_batch on soft bits: maximum-likelihood decoding of every codeword over its
+ * 16 candidates.  llr is [frames][sym_stride][sf] floats (lora_demod_soft_bits_batch's layout,
+ * sym_stride in symbols; pass llr + 2*sf and sym_count = total - 2 to skip the sync columns of
+ * a LEGACY / API result).  With nb = 4 + rdd, only whole blocks of nb symbols are used:
+ *   deinterleave (diagonalDeterleaveSx's map, LoRaCodes.hpp:396-412, applied to LLRs):
+ *     L[blk*sf + (c + bit) % sf][bit] = llr[blk*nb + bit][c], bit < nb, c < sf;
+ *   de-whiten (Sx1272ComputeWhiteningLfsr with bit offset 0, LoRaCodes.hpp:176-189, masked by
+ *     0xFF >> (4 - rdd)): where bit b of byte j of the sequence is set, L[j][b] is negated;
+ *   decode codeword j: for each nibble x = 0..15 with codeword e (LoRaCodes.hpp:229-371 by
+ *     rdd), m(x) starts at +0.0f and, for b = 0 .. nb-1 in this order,
+ *     m = m + (bit b of e ? L[j][b] : -L[j][b]) in fp32, no contraction.  best starts at -inf
+ *     and the nibble at 0; x is scanned upward from 0 and taken where m(x) > best (strict), so
+ *     the lowest nibble wins ties and a NaN (or -inf) metric never wins.  At rdd = 0 this is
+ *     the sign of each LLR;
+ *   nibbles are packed high first into `nbytes` bytes.
+ * corrected[f] (optional) = codewords among the first 2 * nbytes whose chosen codeword differs
+ * from the hard word (bit b = L[j][b] > 0) in any of the nb positions.  One kernel, nothing
+ * allocated or synchronised, no workspace, every output fully written.  Parameter checks and
+ * LORA_ERANGE as in lora_decode_chain_batch.  Returns nbytes. */
+int64_t lora_decode_chain_soft_batch(int sf, int rdd, const float* llr, int64_t frames,
+                                     int64_t sym_count, int64_t sym_stride, int64_t nbytes,
+                                     uint8_t* payload, int64_t payload_stride,
+                                     int32_t* corrected, int device, void* stream);
 
 /* The transmit side of the same chain (the order of runners/lora_phy_vector_generate.cpp:
  * 189-223): bytes -> nibbles, high first -> codewords by rdd (LoRaCodes.hpp:229-371), padded

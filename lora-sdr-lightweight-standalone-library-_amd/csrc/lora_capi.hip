@@ -1787,6 +1787,58 @@ int64_t lora_demod_metrics_batch(lora_demod_plan* plan, const float* iq, int64_t
   return rc < 0 ? rc : total;
 }
 
+int64_t lora_demod_soft_bits_batch(lora_demod_plan* plan, const float* iq, int64_t frames,
+                                   int64_t frame_len, int64_t frame_stride, const float* cfo,
+                                   const float* time_offset, const float* max_amp,
+                                   float* llr, int64_t llr_stride, void* stream) {
+  if (!plan) return set_error(LORA_EINVAL, "null argument");
+  if (frames < 0 || frame_len < 0 || frame_stride < 0 || llr_stride < 0)
+    return set_error(LORA_EINVAL, "negative frames / frame_len / frame_stride / llr_stride");
+  if (frames > 1 && frame_stride < frame_len) return set_error(LORA_EINVAL, "frame_stride smaller than frame_len");
+  if (frame_len >= (int64_t(1) << 31)) return set_error(LORA_EINVAL, "frame_len must be < 2^31");
+  const lora_demod_params& p = plan->prm;
+  if (p.sf < 6) return set_error(LORA_EINVAL, "soft bits need a plan with sf in 6..12");
+  if (p.mode == LORA_MODE_API) {  // the plan's own frame-length rule (phy.cpp:186-188)
+    const int64_t n = lora_demod_symbols_per_frame(plan, frame_len);
+    if (n < 0) return n;
+  }
+  const int64_t total = frame_len / plan->step;
+  if (llr && llr_stride < total) return set_error(LORA_EINVAL, "llr_stride smaller than symbols per frame");
+  if (frames > 0) {
+    if (!iq) return set_error(LORA_EINVAL, "null iq");
+    if (p.mode != LORA_MODE_RAW && (!cfo || !time_offset))
+      return set_error(LORA_EINVAL, "LEGACY / API soft bits need the frames' cfo and time_offset arrays");
+    if (p.mode == LORA_MODE_LEGACY && !max_amp)
+      return set_error(LORA_EINVAL, "LEGACY soft bits need the frames' max_amp array");
+  }
+  if (frames == 0 || total == 0 || !llr) return total;
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  if (prev != p.device) HIP_TRY(hipSetDevice(p.device));
+  KArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.iq = reinterpret_cast<const cf*>(iq);
+  a.frame_len = frame_len;
+  a.frame_stride = frame_stride;
+  a.sf = (int)p.sf;
+  a.N = plan->N;
+  a.osr = (int)p.osr;
+  a.step = plan->step;
+  a.total = (int)total;
+  a.mode = p.mode;
+  a.dechirp = (p.mode != LORA_MODE_API && p.dechirp) ? 1 : 0;
+  a.hann = p.window == LORA_WINDOW_HANN;
+  a.tw = plan->tw;
+  a.rev = plan->rev;
+  a.win = plan->win;
+  a.down = plan->down;
+  a.down1 = plan->down1;
+  const int rc = lora::launch_soft_bits(a, cfo, time_offset, max_amp, llr, llr_stride, frames,
+                                        static_cast<hipStream_t>(stream));
+  if (prev != p.device) hipSetDevice(prev);
+  return rc < 0 ? rc : total;
+}
+
 int64_t lora_detect_scan_windows(const lora_demod_plan* plan, int64_t row_len, int64_t hop) {
   if (!plan) return set_error(LORA_EINVAL, "null plan");
   if (row_len < 0 || hop < 1) return set_error(LORA_EINVAL, "row_len must be >= 0 and hop >= 1");

@@ -1,12 +1,14 @@
 // lora_codec.hip — the payload codec on the device: symbols <-> bytes for whole batches of
 // frames, behind lora_decode_batch / lora_encode_batch / lora_decode_chain_batch /
-// lora_encode_chain_batch (include/lora_mi355x.h).
+// lora_encode_chain_batch / lora_decode_chain_soft_batch (include/lora_mi355x.h).
 //
-// All four are bit-exact integer work, one kernel per call, no workspace, no atomics:
+// The first four are bit-exact integer work, one kernel per call, no workspace, no atomics:
 //   k_codec_decode        LoRaDecoder.cpp:8-19 + the CRC check of phy.cpp:241-256
 //   k_codec_encode        LoRaEncoder.cpp:8-19 (+ the SX1272 data checksum appended)
 //   k_codec_chain_decode  Gray -> diagonal deinterleave -> de-whitening -> nibble decode
 //   k_codec_chain_encode  nibble encode -> whitening -> diagonal interleave -> Gray
+// and k_soft_chain_decode is k_codec_chain_decode on per-bit LLRs (lora_demod_soft_bits_batch's):
+// deinterleave and de-whitening act on the LLRs, the nibble decode is maximum likelihood.
 // (LoRaCodes.hpp:176-189, 201-222, 229-371, 376-412; lora_phy_amd/codes.py restates them
 // on the host and is the checker in tests/test_gpu_codec.py).
 //
@@ -443,6 +445,74 @@ __global__ void __launch_bounds__(kBlock) k_codec_chain_decode(ChainArgs a) {
   if (live && l == 0 && a.err) a.err[f] = (int32_t)ne;
 }
 
+// The chain decoder on soft bits: each codeword's 4 + rdd LLRs are gathered through the
+// deinterleave map straight from global memory (every LLR of the frame's blocks is read by
+// exactly one lane, so nothing is staged), their signs follow the whitening sequence, and the
+// nibble is the candidate with the largest correlation.  fp32 additions only, in bit order.
+// One instance per RDD: the 16 candidate codewords and the bit count are constants.
+struct SoftArgs {
+  ChainArgs c;
+  const float* llr;  // [frames][c.sym_stride][c.sf]
+};
+template <int RDD>
+__global__ void __launch_bounds__(kBlock) k_soft_chain_decode(SoftArgs sa) {
+  const ChainArgs& a = sa.c;
+  const float* __restrict__ llr = sa.llr;
+  const int tid = threadIdx.x;
+  const int G = 1 << a.lg;
+  const int l = tid & (G - 1);
+  const int64_t f = (int64_t)blockIdx.x * (kBlock >> a.lg) + (tid >> a.lg);
+  const bool live = f < a.frames;
+  constexpr int nbits = 4 + RDD;
+  uint32_t nc = 0;
+  if (live) {
+    const uint8_t* wh = kWhiten.v[RDD == 1 ? 1 : 0];
+    const uint32_t mask = 0xFFu >> (4 - RDD);
+    const float* row = llr + f * a.sym_stride * a.sf;
+    uint8_t* out = a.pay_out + f * a.pay_stride;
+    for (int k = l; k < a.nbytes; k += G) {
+      uint32_t byte = 0;
+      for (int h = 0; h < 2; ++h) {
+        // codeword c = row `dst` of block `blk`: its bit `bit` is bit (dst - bit) mod sf of
+        // the block's symbol `bit` (LoRaCodes.hpp:396-412)
+        const int c = 2 * k + h;
+        const int blk = c / a.sf;
+        const int dst = c - blk * a.sf;
+        const float* s = row + (size_t)blk * nbits * a.sf;
+        const uint32_t w = wh[c] & mask;
+        float L[nbits];
+        uint32_t hard = 0;
+#pragma unroll
+        for (int bit = 0; bit < nbits; ++bit) {
+          const int ci = (dst + 2 * a.sf - bit) % a.sf;
+          float v = s[bit * a.sf + ci];
+          if ((w >> bit) & 1u) v = -v;
+          if (v > 0.0f) hard |= 1u << bit;
+          L[bit] = v;
+        }
+        float best = -__builtin_inff();
+        uint32_t nib = 0;
+#pragma unroll
+        for (uint32_t x = 0; x < 16; ++x) {
+          const uint32_t e = nibble_encode(x, RDD);
+          float m = 0.0f;
+#pragma unroll
+          for (int bit = 0; bit < nbits; ++bit) m = m + (((e >> bit) & 1u) ? L[bit] : -L[bit]);
+          if (m > best) {
+            best = m;
+            nib = x;
+          }
+        }
+        byte = (byte << 4) | nib;
+        nc += nibble_encode(nib, RDD) != hard ? 1u : 0u;
+      }
+      out[k] = (uint8_t)byte;
+    }
+  }
+  nc = group_sum(nc, a.lg);
+  if (live && l == 0 && a.err) a.err[f] = (int32_t)nc;
+}
+
 __global__ void __launch_bounds__(kBlock) k_codec_chain_encode(ChainArgs a) {
   __shared__ uint8_t sh[kChainEncLds];
   const int tid = threadIdx.x;
@@ -596,6 +666,39 @@ int64_t lora_decode_chain_batch(int sf, int rdd, const uint16_t* symbols, int64_
   a.err = err_count;
   if ((int64_t)(kBlock >> a.lg) * a.nsym > kChainDecLds) return set_last_error(LORA_EINVAL, "frame too long");
   return launch_frames(k_codec_chain_decode, a, frames, a.lg, device, stream, nbytes);
+}
+
+int64_t lora_decode_chain_soft_batch(int sf, int rdd, const float* llr, int64_t frames, int64_t sym_count,
+                                     int64_t sym_stride, int64_t nbytes, uint8_t* payload, int64_t payload_stride,
+                                     int32_t* corrected, int device, void* stream) {
+  if (!chain_params_ok(sf, rdd, nbytes))
+    return set_last_error(LORA_EINVAL, "sf must be in 6..12, rdd in 0..4, nbytes in 0..255");
+  if (frames < 0 || sym_count < 0) return set_last_error(LORA_EINVAL, "bad frames / sym_count");
+  if (sym_stride < sym_count) return set_last_error(LORA_EINVAL, "sym_stride smaller than sym_count");
+  if (payload_stride < nbytes) return set_last_error(LORA_EINVAL, "payload_stride smaller than nbytes");
+  if (2 * nbytes > sym_count / (4 + rdd) * sf)
+    return set_last_error(LORA_ERANGE, "nbytes needs more codewords than sym_count yields");
+  if (frames == 0) return nbytes;
+  if (nbytes > 0 && (!llr || !payload)) return set_last_error(LORA_EINVAL, "null buffer");
+  if (nbytes == 0 && !corrected) return nbytes;  // nothing to write
+  ChainArgs a{};
+  a.sf = sf;
+  a.rdd = rdd;
+  a.nbytes = (int)nbytes;
+  a.lg = group_lg(nbytes);
+  a.frames = frames;
+  a.sym_stride = sym_stride;
+  a.pay_stride = payload_stride;
+  a.pay_out = payload;
+  a.err = corrected;
+  const SoftArgs sa{a, llr};
+  switch (rdd) {
+    case 0: return launch_frames(k_soft_chain_decode<0>, sa, frames, a.lg, device, stream, nbytes);
+    case 1: return launch_frames(k_soft_chain_decode<1>, sa, frames, a.lg, device, stream, nbytes);
+    case 2: return launch_frames(k_soft_chain_decode<2>, sa, frames, a.lg, device, stream, nbytes);
+    case 3: return launch_frames(k_soft_chain_decode<3>, sa, frames, a.lg, device, stream, nbytes);
+    default: return launch_frames(k_soft_chain_decode<4>, sa, frames, a.lg, device, stream, nbytes);
+  }
 }
 
 int64_t lora_encode_chain_batch(int sf, int rdd, const uint8_t* payload, int64_t frames, int64_t nbytes,

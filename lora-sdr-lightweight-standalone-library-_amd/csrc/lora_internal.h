@@ -136,6 +136,12 @@ bool launch_est_fast(const KArgs& a, int64_t frames, hipStream_t st);
 int launch_detect_metrics(const KArgs& a, const float* cfo, const float* toff, const float* max_amp,
                           const lora_symbol_metrics& o, int64_t frames, hipStream_t st);
 
+// Soft bits per symbol (lora_metrics.hip, k_soft_bits): the same windows and spectra as
+// launch_detect_metrics, reduced to a.sf max-log LLRs per symbol at
+// llr[(frame * llr_stride + symbol) * a.sf + bit].  a.sf is 6..12 (the caller has checked).
+int launch_soft_bits(const KArgs& a, const float* cfo, const float* toff, const float* max_amp, float* llr,
+                     int64_t llr_stride, int64_t frames, hipStream_t st);
+
 // Symbols (windows) per workgroup of the detector-metrics kernels (k_detect_metrics,
 // k_detect_scan): G * N = 4096 points (32 KiB of spectra + 16 KiB of |X|^2), at most one
 // wave's worth of symbols, since the ordered sums take one lane per symbol.

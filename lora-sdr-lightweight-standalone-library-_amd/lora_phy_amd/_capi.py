@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "lora_demod_workspace_bytes",
     "lora_demod_batch",
     "lora_demod_metrics_batch",
+    "lora_demod_soft_bits_batch",
     "lora_detect_scan_windows",
     "lora_detect_scan_batch",
     "lora_mod_batch",
@@ -44,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "lora_decode_batch",
     "lora_encode_batch",
     "lora_decode_chain_batch",
+    "lora_decode_chain_soft_batch",
     "lora_encode_chain_batch",
     "lora_chain_symbols",
     "lora_demod_profile_enable",
@@ -129,6 +131,10 @@ def lib() -> C.CDLL:
     L.lora_demod_metrics_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SymbolMetrics),
                                            C.c_void_p]
+    L.lora_demod_soft_bits_batch.restype = C.c_int64
+    L.lora_demod_soft_bits_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                             C.c_void_p]
     L.lora_detect_scan_windows.restype = C.c_int64
     L.lora_detect_scan_windows.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
     L.lora_detect_scan_batch.restype = C.c_int64
@@ -154,6 +160,9 @@ def lib() -> C.CDLL:
     L.lora_decode_chain_batch.restype = C.c_int64
     L.lora_decode_chain_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                           C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+    L.lora_decode_chain_soft_batch.restype = C.c_int64
+    L.lora_decode_chain_soft_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                               C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
     L.lora_encode_chain_batch.restype = C.c_int64
     L.lora_encode_chain_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                           C.c_void_p, C.c_int64, C.c_int, C.c_void_p]

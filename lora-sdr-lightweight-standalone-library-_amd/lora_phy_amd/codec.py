@@ -1,7 +1,8 @@
 """The payload codec on the GPU: symbols <-> bytes for whole batches of frames.
 
 Torch-tensor wrappers over lora_decode_batch / lora_encode_batch / lora_decode_chain_batch /
-lora_encode_chain_batch (include/lora_mi355x.h, csrc/lora_codec.hip): one kernel per call on
+lora_encode_chain_batch / lora_decode_chain_soft_batch (the chain decoder on per-bit LLRs)
+(include/lora_mi355x.h, csrc/lora_codec.hip): one kernel per call on
 the current torch stream, nothing leaves the device.  There is no CPU fallback (TypeError on
 a CPU tensor); the host implementation of the same functions, :mod:`lora_phy_amd.codes`, is
 the checker in the tests.
@@ -166,4 +167,40 @@ def decode_chain(symbols: torch.Tensor, sf: int, cr, nbytes: int, out: Optional[
     _capi.check(_capi.lib().lora_decode_chain_batch(int(sf), rdd, _ptr(s), F, S, _row_stride(s), nbytes, _ptr(pay),
                                                     _row_stride(pay), out.errors.data_ptr(), dev.index,
                                                     _stream(dev)))
+    return out
+
+
+def decode_chain_soft(llr: torch.Tensor, sf: int, cr, nbytes: int, out: Optional[DecodeResult] = None) -> DecodeResult:
+    """``decode_chain`` on per-bit LLRs (lora_decode_chain_soft_batch): ``llr`` is a float32
+    [F, S, sf] (or [S, sf]) CUDA tensor as ``DemodPlan.soft_bits`` returns it, positive = 1;
+    rows may be a view such as ``bits[:, 2:]`` (unit stride in the last dimension, pitch sf in
+    the one before, rows not overlapping).  Deinterleaving and de-whitening act on the LLRs
+    (a set whitening bit flips a sign); every codeword decodes to the nibble whose codeword
+    correlates best with its 4 + RDD LLRs, the lowest nibble on a tie.  ``errors`` counts the
+    codewords among the first 2 * nbytes whose chosen codeword differs from the signs of
+    their LLRs; ``crc_ok`` and ``bad`` are None."""
+    rdd = codes.rdd_of(cr)
+    sf, nbytes = int(sf), int(nbytes)
+    _require_cuda(llr, "llr")
+    if llr.dtype != torch.float32:
+        raise TypeError(f"llr must be torch.float32, got {llr.dtype}")
+    squeeze = llr.dim() == 2
+    t = llr.unsqueeze(0) if squeeze else llr
+    if (t.dim() != 3 or t.shape[2] != sf or (sf > 1 and t.stride(2) != 1) or (t.shape[1] > 1 and t.stride(1) != sf)
+            or (t.shape[0] > 1 and (t.stride(0) % sf or t.stride(0) < t.shape[1] * sf))):
+        raise ValueError(f"llr must be [frames, symbols, {sf}] (or [symbols, {sf}]) with unit stride in the last "
+                         f"dimension, pitch {sf} in the one before and non-overlapping rows")
+    if not 0 <= nbytes <= MAX_PAYLOAD:
+        raise ValueError(f"nbytes must be in 0..{MAX_PAYLOAD}")
+    F, S = t.shape[0], t.shape[1]
+    dev = t.device
+    if out is None:
+        out = DecodeResult(payload=torch.empty((nbytes,) if squeeze else (F, nbytes), dtype=torch.uint8,
+                                               device=dev),
+                           crc_ok=None, errors=torch.empty(F, dtype=torch.int32, device=dev), bad=None)
+    pay = _out_rows(out.payload, "out.payload", torch.uint8, F, nbytes, squeeze, dev)
+    _check_buf(out.errors, "out.errors", torch.int32, dev, F)
+    _capi.check(_capi.lib().lora_decode_chain_soft_batch(sf, rdd, _ptr(t), F, S, t.stride(0) // sf if F > 1 else S,
+                                                         nbytes, _ptr(pay), _row_stride(pay),
+                                                         out.errors.data_ptr(), dev.index, _stream(dev)))
     return out

@@ -260,20 +260,66 @@ class DemodPlan:
         if self.mode == "api":
             self.symbols_per_frame(L)  # the plan's frame-length rule
         total = L // self.step
-        cfo = toff = amp = None
-        if self.mode != "raw":
-            if result is None:
-                raise ValueError(f"a {self.mode} plan needs result= (the DemodResult of run() on these frames)")
-            names = ("cfo", "time_offset") + (("max_amp",) if self.mode == "legacy" else ())
-            for name in names:
-                _check_buf(getattr(result, name), "result." + name, torch.float32, dev, F)
-            cfo, toff = result.cfo.data_ptr(), result.time_offset.data_ptr()
-            amp = result.max_amp.data_ptr() if self.mode == "legacy" else None
+        cfo, toff, amp = self._frame_offsets(result, F)
         out, m = _metric_outputs(out, F, total, dev)
         stride = iq.stride(0) if F > 1 else L
         _capi.check(self._lib.lora_demod_metrics_batch(self._h, iq.data_ptr(), F, L, stride, cfo, toff, amp,
                                                        C.byref(m), _stream_handle(dev)))
         return out
+
+    def _frame_offsets(self, result: Optional[DemodResult], F: int):
+        """(cfo, time_offset, max_amp) device pointers of ``result`` as the plan's mode needs
+        them to rebuild each symbol's window; all None for a raw plan."""
+        if self.mode == "raw":
+            return None, None, None
+        if result is None:
+            raise ValueError(f"a {self.mode} plan needs result= (the DemodResult of run() on these frames)")
+        names = ("cfo", "time_offset") + (("max_amp",) if self.mode == "legacy" else ())
+        for name in names:
+            _check_buf(getattr(result, name), "result." + name, torch.float32, self.device, F)
+        return (result.cfo.data_ptr(), result.time_offset.data_ptr(),
+                result.max_amp.data_ptr() if self.mode == "legacy" else None)
+
+    def soft_bits(self, iq: torch.Tensor, result: Optional[DemodResult] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Max-log LLRs of the sf bits of every whole symbol (lora_demod_soft_bits_batch) for
+        the frames of a [F, L] (or [L]) complex64 CUDA tensor: float32 [F, total, sf], column s
+        = symbol s (the sync symbols are columns 0 and 1), positive = the bit of
+        grayToBinary16(index) is 1, on the same spectra as ``detect_metrics``.  SF 6-12.
+
+        ``result`` follows ``detect_metrics``' rules (required for legacy / api plans, ignored
+        for raw ones).  ``out``: a float32 [>= F, >= total, sf] tensor, contiguous in its last
+        two dimensions; the [F, total, sf] view of it that was written is returned.  One kernel
+        on the current stream, nothing allocated besides the output, so the call can be captured
+        in a HIP graph."""
+        iq = _check_iq(iq, self.device)
+        F, L = iq.shape
+        dev = self.device
+        if not 6 <= self.sf <= 12:
+            raise ValueError("soft bits need a plan with sf in 6..12")
+        if self.mode == "api":
+            self.symbols_per_frame(L)  # the plan's frame-length rule
+        total = L // self.step
+        cfo, toff, amp = self._frame_offsets(result, F)
+        if out is None:
+            out = torch.empty((F, total, self.sf), dtype=torch.float32, device=dev)
+        else:
+            _require_cuda(out, "out")
+            if out.dtype != torch.float32:
+                raise TypeError(f"out must be torch.float32, got {out.dtype}")
+            if (out.device != dev or out.dim() != 3 or out.shape[0] < F or out.shape[1] < total
+                    or out.shape[2] != self.sf or out.stride(2) != 1
+                    or (out.shape[1] > 1 and out.stride(1) != self.sf)
+                    or (F > 1 and (out.stride(0) % self.sf or out.stride(0) < total * self.sf))):
+                raise ValueError(f"out must be a float32 [>={F}, >={total}, {self.sf}] tensor on {dev}, contiguous "
+                                 "in its last two dimensions, with non-overlapping rows")
+        llr_stride = out.stride(0) // self.sf if F > 1 else total
+        stride = iq.stride(0) if F > 1 else L
+        got = _capi.check(self._lib.lora_demod_soft_bits_batch(
+            self._h, iq.data_ptr(), F, L, stride, cfo, toff, amp, out.data_ptr() if out.numel() else None,
+            llr_stride, _stream_handle(dev)))
+        assert got == total, (got, total)
+        return out[:F, :total]
 
     def scan_windows(self, row_len: int, hop: int) -> int:
         """Windows ``scan`` computes per row of ``row_len`` samples: one every ``hop`` samples
@@ -405,6 +451,24 @@ class LoRaDemod:
                 raise ValueError(f"nbytes={nbytes} needs {2 * int(nbytes)} symbols, the frames have {syms.shape[-1]}")
             syms = syms[..., :2 * int(nbytes)]
         return codec.decode(syms)
+
+    def work_payload_soft(self, iq: torch.Tensor, nbytes: Optional[int] = None):
+        """``work_payload(..., chain="lora")`` with soft decisions: demodulate (``last`` is set
+        as by ``work_payload``), take the per-bit LLRs of the same frames
+        (``DemodPlan.soft_bits``) and decode their data columns through the chain at this
+        block's ``sf`` and ``cr`` by maximum likelihood (``codec.decode_chain_soft``) to
+        ``nbytes`` bytes (default: as many as the frame's whole blocks carry, at most 255).
+        Returns a codec.DecodeResult whose ``errors`` counts the codewords the soft decision
+        changed.  The sync word in ``last`` stays a hard decision."""
+        from . import codec
+
+        self.last = self.plan.run(iq)
+        llr = self.plan.soft_bits(iq, self.last)
+        if self.plan.mode != "raw":
+            llr = llr[:, 2:]  # the sync symbols' columns
+        if nbytes is None:
+            nbytes = codec.chain_capacity(self.sf, self.cr, llr.shape[1])
+        return codec.decode_chain_soft(llr[0] if iq.dim() == 1 else llr, self.sf, self.cr, nbytes)
 
     def work_metrics(self, iq: torch.Tensor) -> DetectMetrics:
         """Demodulate (``last`` is set as by ``work_frames``), then return the detector's
