@@ -245,6 +245,49 @@ int64_t lora_detect_scan_windows(const lora_demod_plan* plan, int64_t row_len, i
 int64_t lora_detect_scan_batch(lora_demod_plan* plan, const float* iq, int64_t rows, int64_t row_len,
                                int64_t row_stride, int64_t hop, const lora_symbol_metrics* out, void* stream);
 
+/* Digital down-converter bank: one wideband stream in, `channels` streams at the demodulator's
+ * rate out, from one read of the wideband data.  The reference has no channelizer; this
+ * definition is the library's own (like the finder's rule and the soft bits).
+ *   iq    `rows` rows of `row_len` complex samples, row r at iq + 2*r*row_stride floats (device);
+ *   taps  `ntaps` real fp32 values h[j] (device);
+ *   nco   `period` complex fp32 values w[m] = (wr[m], wi[m]) (device): the oscillator table is
+ *         an input, normally exp(-2 pi i m / period) rounded to fp32, so bit parity depends on
+ *         nobody's cosine;
+ *   steps a HOST array of `channels` ints k_c: channel c is centred k_c / period cycles per
+ *         input sample above the tuner.  Any int; each is reduced mod `period` (to 0 .. period-1)
+ *         on the host and travels in the kernel's arguments, so the call can be captured in a
+ *         graph;
+ *   out   [rows][channels][out_stride] complex samples: output t of channel c of row r is at
+ *         out + 2*((r*channels + c)*out_stride + t) floats (device).
+ * A row gives W = row_len < ntaps ? 0 : (row_len - ntaps) / decim + 1 outputs per channel and
+ * no output reads past its row.  All arithmetic is fp32, one rounding per operation, no
+ * contraction.  For sample n of a row, m = (k_c * (first_sample + n)) mod period (in integers,
+ * non-negative):
+ *   zr = xr*wr[m] - xi*wi[m]        zi = xr*wi[m] + xi*wr[m]
+ * and for output t both accumulators start at +0.0f and, for j = 0 .. ntaps-1 in this order,
+ *   yr = yr + h[j]*zr[t*decim + j]    yi = yi + h[j]*zi[t*decim + j].
+ * Infinities and NaN propagate as this arithmetic makes them; there is no special case.  (Where
+ * a result is NaN, its sign and payload are the processor's choice, as IEEE 754 leaves them:
+ * the GPU's subtraction, for one, returns a NaN subtrahend with its sign flipped.)
+ * first_sample (>= 0) keeps the oscillator's phase continuous when a long recording is
+ * processed in chunks: a chunk that starts at a multiple of decim and overlaps its predecessor
+ * by ntaps - decim samples continues the predecessor's outputs.
+ *
+ * lora_channelize_outputs: host arithmetic only; W, or LORA_EINVAL for a negative row_len,
+ * ntaps < 1 or decim < 1.
+ * lora_channelize_batch: enqueues one kernel on `stream` of `device`, allocates and synchronises
+ * nothing, needs no workspace, and fully writes columns 0 .. W-1 of every (row, channel) and
+ * nothing beyond them.  rows == 0 or W == 0: no launch.  LORA_EINVAL, before any HIP call: a
+ * NULL taps, nco, steps or out, a NULL iq with work to do, negative sizes or first_sample,
+ * ntaps outside 1..512, decim outside 1..64, period outside 1..4096, channels outside 1..32,
+ * row_len >= 2^31, row_stride < row_len with more than one row, out_stride < W, a grid beyond
+ * 2^31 (rows * ceil(W / outputs per workgroup)).  Returns W. */
+int64_t lora_channelize_outputs(int64_t row_len, int64_t ntaps, int64_t decim);
+int64_t lora_channelize_batch(const float* iq, int64_t rows, int64_t row_len, int64_t row_stride,
+                              int64_t first_sample, const float* taps, int64_t ntaps, int64_t decim,
+                              const float* nco, int64_t period, const int32_t* steps, int64_t channels,
+                              float* out, int64_t out_stride, int device, void* stream);
+
 /* lora_modulate for `frames` independent frames: symbols [frames][sym_count] ->
  * iq [frames][(sym_count+2)*N*osr] (2 sync up-chirps then one chirp per symbol,
  * phase-continuous within a frame, LoRaMod.cpp:8-41).  Returns samples per frame. */

@@ -1,0 +1,249 @@
+// lora_channelize.hip — the digital down-converter bank (lora_channelize_batch).
+//
+// One wideband row in, `channels` rows at the demodulator's rate out: every sample is mixed
+// with each channel's oscillator (a table the caller supplies), then a real FIR of `ntaps`
+// taps is evaluated every `decim` samples.  The arithmetic is the header's, operation for
+// operation: fp32, one rounding each, no contraction, the taps accumulated in order from
+// +0.0f.  The reference has no channelizer; the definition is this library's own
+// (tests/channel_checker.py restates it in numpy and the GPU tests compare bits).
+//
+// A workgroup owns `tile` consecutive outputs of every channel of one row.  It reads the
+// (tile-1)*decim + ntaps samples they cover once, with 16-byte loads, and mixes each sample
+// once per channel into LDS.  The mixed samples of a channel are kept by phase: sample s sits
+// at [s % decim][s / decim], a row of pitch ps = tile + (ntaps-1)/decim per phase, so that the
+// FIR's read of tap j for consecutive outputs (samples decim apart) is a read of consecutive
+// LDS entries.  The FIR runs from LDS, one output index per lane and two channels per lane at
+// a time; the taps are loaded 64 at a time, one per lane, and handed round by readlane.
+// tile is 64 where all channels fit the 64 KiB of LDS at once (channel_geometry below);
+// otherwise it shrinks to 32, 16 or 8, and if the channels still do not fit they are taken in
+// passes of `cg`, each pass re-reading the tile's samples (the ABI's extremes, 32 channels of
+// 512 taps at decim 64, run that way).
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/lora_mi355x.h"
+#include "lora_device.h"
+#include "lora_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace lora {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxTile = 64, kMinTile = 8;
+constexpr int kLdsSamples = 8192;  // mixed samples a workgroup holds: 64 KiB
+constexpr int kMaxTaps = 512, kMaxDecim = 64, kMaxPeriod = 4096, kMaxChannels = 32;
+
+struct ChanArgs {
+  const cf* iq;
+  const float* taps;
+  const cf* nco;
+  cf* out;
+  int64_t row_stride, out_stride, W, gpr;
+  int ntaps, decim, period, channels;
+  int first_mod;  // first_sample mod period
+  int tile, lg_tile, ps, cg;
+  float inv_decim, inv_period;
+  int steps[kMaxChannels];  // each in 0 .. period-1
+};
+
+// LDS entries of one channel: decim phase rows of `tile` outputs plus the taps' reach
+__host__ __device__ constexpr int channel_entries(int tile, int ntaps, int decim) {
+  return decim * (tile + (ntaps - 1) / decim);
+}
+
+// a / d and a % d for 0 <= a < 2^24, d <= 4096 and a / d < 2^13, inv = 1.0f / d: the product is
+// within a / d * 2^-23 < 1 of the quotient, so its truncation is off by at most one either way
+// (the products here are of 24-bit operands: __umul24 runs at full rate, a 32-bit multiply at a
+// quarter of it)
+__device__ __forceinline__ void divmod(unsigned a, unsigned d, float inv, unsigned& q, unsigned& r) {
+  q = (unsigned)((float)a * inv);
+  int rr = (int)a - (int)__umul24(q, d);
+  if (rr < 0) {
+    rr += (int)d;
+    --q;
+  } else if (rr >= (int)d) {
+    rr -= (int)d;
+    ++q;
+  }
+  r = (unsigned)rr;
+}
+
+__global__ void __launch_bounds__(kThreads) k_channelize(ChanArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  v2f* Z = reinterpret_cast<v2f*>(smem);  // [cg][decim][ps]
+  const int tid = threadIdx.x;
+  const int64_t row = (int64_t)blockIdx.x / a.gpr;
+  const int64_t t0 = ((int64_t)blockIdx.x - row * a.gpr) * a.tile;
+  const int nv = a.W - t0 < a.tile ? (int)(a.W - t0) : a.tile;  // >= 1
+  // the tile's first sample and how many it covers; the last output's window ends inside the
+  // row ((W-1)*decim + ntaps <= row_len), so nothing below reads past it
+  const int64_t n0 = t0 * a.decim;  // < row_len < 2^31
+  const cf* x = a.iq + row * a.row_stride + n0;
+  const int cnt = (nv - 1) * a.decim + a.ntaps;
+  const int chs = channel_entries(a.tile, a.ntaps, a.decim);
+  // the oscillator's position at the tile's first sample: (first_sample + n0) mod period
+  const unsigned p0 = ((unsigned)a.first_mod + (unsigned)n0 % (unsigned)a.period) % (unsigned)a.period;
+  const int tl = tid & (a.tile - 1), cl = tid >> a.lg_tile, ncl = kThreads >> a.lg_tile;
+  const float* __restrict__ taps = a.taps;
+  const cf* __restrict__ nco = a.nco;
+
+  for (int c0 = 0; c0 < a.channels; c0 += a.cg) {
+    const int nc = a.channels - c0 < a.cg ? a.channels - c0 : a.cg;
+    if (c0) __syncthreads();  // the previous pass's FIR has read Z
+
+    // sample s of the tile, mixed for the pass's channels
+    auto mix = [&](int s, float xr, float xi) {
+      unsigned q, ph, u, p;
+      divmod((unsigned)s, (unsigned)a.decim, a.inv_decim, q, ph);
+      divmod(p0 + (unsigned)s, (unsigned)a.period, a.inv_period, u, p);
+      v2f* dst = Z + ph * a.ps + q;
+#pragma unroll 4
+      for (int c = 0; c < nc; ++c) {
+        unsigned m;
+        divmod(__umul24((unsigned)a.steps[c0 + c], p), (unsigned)a.period, a.inv_period, u, m);
+        const cf w = nco[m];
+        v2f z;
+        z.x = xr * w.re - xi * w.im;
+        z.y = xr * w.im + xi * w.re;
+        dst[c * chs] = z;
+      }
+    };
+    // pairs on the 16-byte grid of the address space: pair q holds samples 2q - mis and
+    // 2q + 1 - mis; a pair that hangs over either end is loaded singly
+    const int mis = (int)((reinterpret_cast<uintptr_t>(x) >> 3) & 1);
+    const int pairs = (cnt + mis + 1) >> 1;
+    for (int q = tid; q < pairs; q += kThreads) {
+      const int s0 = 2 * q - mis;
+      if (s0 >= 0 && s0 + 1 < cnt) {
+        const float4 v = *reinterpret_cast<const float4*>(x + s0);
+        mix(s0, v.x, v.y);
+        mix(s0 + 1, v.z, v.w);
+      } else {
+        if (s0 >= 0) mix(s0, x[s0].re, x[s0].im);
+        if (s0 + 1 < cnt) mix(s0 + 1, x[s0 + 1].re, x[s0 + 1].im);
+      }
+    }
+    __syncthreads();
+
+    // output t0 + tl of channels c and c + ncl: tap j meets sample tl * decim + j, entry
+    // [j % decim][tl + j / decim].  Every lane of the workgroup runs the loop, because every
+    // lane's tap is read by readlane; a lane with no output (tl >= nv, or no channel left)
+    // works on entries inside Z that belong to others or were never written, and stores nothing.
+    for (int cb = 0; cb < nc; cb += 2 * ncl) {
+      const int c = cb + cl;
+      const bool one = tl < nv && c < nc, two = tl < nv && c + ncl < nc;
+      const v2f* z0 = Z + (c < nc ? c : 0) * chs + tl;
+      const v2f* z1 = Z + (c + ncl < nc ? c + ncl : 0) * chs + tl;
+      v2f y0 = {0.0f, 0.0f}, y1 = {0.0f, 0.0f};
+      // 64 taps at a time, one per lane, handed round by readlane; `at` walks the phase rows
+      int ph = 0, at = 0;
+      for (int jb = 0; jb < a.ntaps; jb += 64) {
+        const int n = a.ntaps - jb < 64 ? a.ntaps - jb : 64;
+        const int hv = (tid & 63) < n ? __float_as_int(taps[jb + (tid & 63)]) : 0;
+        for (int jj = 0; jj < n; ++jj) {
+          const float h = __int_as_float(__builtin_amdgcn_readlane(hv, jj));
+          y0 = y0 + h * z0[at];
+          y1 = y1 + h * z1[at];
+          at += a.ps;
+          if (++ph == a.decim) {
+            ph = 0;
+            at -= a.decim * a.ps - 1;
+          }
+        }
+      }
+      v2f* o = reinterpret_cast<v2f*>(a.out) + ((row * a.channels + c0 + c) * a.out_stride + t0 + tl);
+      if (one) *o = y0;
+      if (two) o[(int64_t)ncl * a.out_stride] = y1;
+    }
+  }
+}
+
+int64_t channel_outputs(int64_t row_len, int64_t ntaps, int64_t decim) {
+  return row_len < ntaps ? 0 : (row_len - ntaps) / decim + 1;
+}
+
+// Outputs per workgroup and channels per pass: the largest tile of 64, 32, 16, 8 at which all
+// channels fit the LDS; at 8 whatever fits (at least 8: a channel takes at most 960 entries)
+void channel_geometry(int ntaps, int decim, int channels, int& tile, int& cg) {
+  tile = kMaxTile;
+  while (tile > kMinTile && (int64_t)channels * channel_entries(tile, ntaps, decim) > kLdsSamples) tile >>= 1;
+  cg = kLdsSamples / channel_entries(tile, ntaps, decim);
+  if (cg > channels) cg = channels;
+}
+
+}  // namespace
+}  // namespace lora
+
+using lora::set_last_error;
+
+extern "C" {
+
+int64_t lora_channelize_outputs(int64_t row_len, int64_t ntaps, int64_t decim) {
+  if (row_len < 0 || ntaps < 1 || decim < 1)
+    return set_last_error(LORA_EINVAL, "row_len must be >= 0, ntaps >= 1 and decim >= 1");
+  return lora::channel_outputs(row_len, ntaps, decim);
+}
+
+int64_t lora_channelize_batch(const float* iq, int64_t rows, int64_t row_len, int64_t row_stride,
+                              int64_t first_sample, const float* taps, int64_t ntaps, int64_t decim,
+                              const float* nco, int64_t period, const int32_t* steps, int64_t channels,
+                              float* out, int64_t out_stride, int device, void* stream) {
+  using namespace lora;
+  if (!taps || !nco || !steps || !out) return set_last_error(LORA_EINVAL, "null taps / nco / steps / out");
+  if (rows < 0 || row_len < 0 || row_stride < 0 || out_stride < 0 || first_sample < 0)
+    return set_last_error(LORA_EINVAL, "negative rows / row_len / row_stride / out_stride / first_sample");
+  if (ntaps < 1 || ntaps > kMaxTaps) return set_last_error(LORA_EINVAL, "ntaps must be in 1..512");
+  if (decim < 1 || decim > kMaxDecim) return set_last_error(LORA_EINVAL, "decim must be in 1..64");
+  if (period < 1 || period > kMaxPeriod) return set_last_error(LORA_EINVAL, "period must be in 1..4096");
+  if (channels < 1 || channels > kMaxChannels) return set_last_error(LORA_EINVAL, "channels must be in 1..32");
+  if (row_len >= (int64_t(1) << 31)) return set_last_error(LORA_EINVAL, "row_len must be < 2^31");
+  if (rows > 1 && row_stride < row_len) return set_last_error(LORA_EINVAL, "row_stride smaller than row_len");
+  const int64_t W = channel_outputs(row_len, ntaps, decim);
+  if (out_stride < W) return set_last_error(LORA_EINVAL, "out_stride smaller than outputs per row");
+  ChanArgs a{};
+  channel_geometry((int)ntaps, (int)decim, (int)channels, a.tile, a.cg);
+  a.W = W;
+  a.gpr = (W + a.tile - 1) / a.tile;
+  // rows * gpr < 2^31, compared through the quotient so that nothing overflows
+  const int64_t lim = int64_t(1) << 31;
+  if (rows > 0 && a.gpr > 0 && (a.gpr >= lim || rows > (lim - 1) / a.gpr))
+    return set_last_error(LORA_EINVAL, "batch too large");
+  if (rows == 0 || W == 0) return W;
+  if (!iq) return set_last_error(LORA_EINVAL, "null iq");
+  a.iq = reinterpret_cast<const cf*>(iq);
+  a.taps = taps;
+  a.nco = reinterpret_cast<const cf*>(nco);
+  a.out = reinterpret_cast<cf*>(out);
+  a.row_stride = row_stride;
+  a.out_stride = out_stride;
+  a.ntaps = (int)ntaps;
+  a.decim = (int)decim;
+  a.period = (int)period;
+  a.channels = (int)channels;
+  a.first_mod = (int)(first_sample % period);
+  for (a.lg_tile = 0; (1 << a.lg_tile) < a.tile; ++a.lg_tile) {
+  }
+  a.ps = a.tile + (a.ntaps - 1) / a.decim;
+  a.inv_decim = 1.0f / (float)a.decim;
+  a.inv_period = 1.0f / (float)a.period;
+  for (int c = 0; c < a.channels; ++c) {
+    const int64_t k = (int64_t)steps[c] % period;
+    a.steps[c] = (int)(k < 0 ? k + period : k);
+  }
+  const size_t lds = (size_t)a.cg * channel_entries(a.tile, a.ntaps, a.decim) * sizeof(cf);
+  int prev = 0;
+  hipError_t e = hipGetDevice(&prev);
+  if (e == hipSuccess && prev != device) e = hipSetDevice(device);
+  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("channelize device: ") + hipGetErrorString(e));
+  hipLaunchKernelGGL(k_channelize, dim3((unsigned)(rows * a.gpr)), dim3(kThreads), lds,
+                     static_cast<hipStream_t>(stream), a);
+  e = hipGetLastError();
+  if (prev != device) hipSetDevice(prev);
+  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("k_channelize: ") + hipGetErrorString(e));
+  return W;
+}
+
+}  // extern "C"

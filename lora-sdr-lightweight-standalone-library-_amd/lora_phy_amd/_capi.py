@@ -39,6 +39,8 @@ EXPORTED_SYMBOLS = (
     "lora_demod_soft_bits_batch",
     "lora_detect_scan_windows",
     "lora_detect_scan_batch",
+    "lora_channelize_outputs",
+    "lora_channelize_batch",
     "lora_mod_batch",
     "lora_estimate_offsets_batch",
     "lora_compensate_offsets_batch",
@@ -140,6 +142,13 @@ def lib() -> C.CDLL:
     L.lora_detect_scan_batch.restype = C.c_int64
     L.lora_detect_scan_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                          C.POINTER(SymbolMetrics), C.c_void_p]
+    # the down-converter bank (csrc/lora_channelize.hip)
+    L.lora_channelize_outputs.restype = C.c_int64
+    L.lora_channelize_outputs.argtypes = [C.c_int64, C.c_int64, C.c_int64]
+    L.lora_channelize_batch.restype = C.c_int64
+    L.lora_channelize_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int32),
+                                        C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     L.lora_mod_batch.restype = C.c_int64
     L.lora_mod_batch.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_float, C.c_uint8, C.c_void_p,
                                  C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]

@@ -492,6 +492,21 @@ class LoRaDemod:
         self.last = res
         return starts, res.symbols[:, :self.mtu]
 
+    def work_wideband(self, chan, iq: torch.Tensor, frame_symbols: int, hop: Optional[int] = None,
+                      thresh_db: float = 0.0):
+        """``work_stream`` for a wideband capture (``lora_phy_amd.stream.receive_wideband`` with
+        this block's plan and sync word): ``chan``, a ``stream.Channelizer``, turns the [L] stream
+        into its channel rows, whose frames are found and demodulated.  Returns ``(channel,
+        starts, symbols[:, :mtu])`` - per frame its channel and the sample index, in channel
+        samples, of its first sync symbol, ordered by channel then start; ``last`` keeps the
+        DemodResult of the K frames.  This block's ``osr`` and bw must be the channel rows'."""
+        from . import stream
+
+        channel, starts, res = stream.receive_wideband(self.plan, chan, iq, frame_symbols, hop, self.sync,
+                                                       thresh_db)
+        self.last = res
+        return channel, starts, res.symbols[:, :self.mtu]
+
     def sync_ok(self) -> torch.Tensor:
         """Per-frame flag: recovered sync word equals the configured one."""
         if self.last is None:

@@ -32,6 +32,15 @@ of about 1/N per pair of consecutive symbols; a sync word with equal nibbles mak
 symbol a candidate.  No detection-probability figure is claimed, because none has been
 measured.  A perfectly aligned noiseless window has no noise floor (``power_avg = -inf``, so
 ``snr = +inf`` and it passes any threshold); a silent window gives NaN and never passes.
+
+Wideband captures.  An SDR delivers one wideband stream that holds several LoRa channels at
+known offsets from the tuner frequency.  ``Channelizer`` is the stage in front of the scan: one
+kernel mixes every channel down, low-pass filters and decimates it (lora_channelize_batch; the
+exact arithmetic is in include/lora_mi355x.h and, like the finder's rule, is this project's own:
+the reference has no channelizer), and ``receive_wideband`` is ``receive`` over all the channel
+rows at once.  Channel centres are multiples of ``fs / period``; the input rate must be
+``decim * bw * osr`` (there is no rational resampling); the finder's 125 kHz restriction is
+inherited; and again no detection-probability figure is claimed.
 """
 from __future__ import annotations
 
@@ -40,9 +49,11 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .demod import DemodPlan, DemodResult, DetectMetrics, _check_iq
+from . import _capi
+from .demod import DemodPlan, DemodResult, DetectMetrics, _check_iq, _require_cuda, _stream_handle
 
-__all__ = ["find_frames", "extract_frames", "receive"]
+__all__ = ["find_frames", "extract_frames", "receive", "lowpass_taps", "nco_table", "Channelizer",
+           "receive_wideband"]
 
 _NONE = -(1 << 62)  # "no candidate here" in the packed starts
 
@@ -68,6 +79,34 @@ def _ceil_div(a: int, b: int) -> int:
     return -((-a) // b)
 
 
+def _candidates(power, floor, index, hop, N, osr, k, sw0, sw1, thresh_db) -> torch.Tensor:
+    """The candidate mask and each candidate's refined start along the last dimension ([W] or
+    [R, W] tensors), on the tensors' device: int64 [.., W - k], ``_NONE`` where no candidate."""
+    n = power.shape[-1] - k
+    ok = (power - floor) >= float(thresh_db)
+    idx = index.to(torch.int64)
+    cand = ok[..., :n] & ok[..., k:] & (torch.remainder(idx[..., k:] - idx[..., :n], N) == (sw1 - sw0) % N)
+    d = torch.remainder(idx[..., :n] - sw0, N)
+    d = torch.where(d >= N // 2, d - N, d)
+    start = torch.arange(n, dtype=torch.int64, device=power.device) * hop - d * osr
+    return torch.where(cand, start, torch.full_like(start, _NONE))
+
+
+def _greedy(packed: np.ndarray, hop: int, step: int, frame_len: int, first: int, row_len: int) -> np.ndarray:
+    """The greedy pass over one row's candidates, on the host."""
+    first = int(first)
+    wmin = _ceil_div(max(first - step // 2, 0), hop)
+    out = []
+    for w in np.flatnonzero(packed != _NONE):
+        w, s = int(w), int(packed[w])
+        if w < wmin or s < first or s + frame_len > row_len:
+            continue
+        out.append(s)
+        first = s + frame_len
+        wmin = max(w + 1, _ceil_div(max(first - step // 2, 0), hop))
+    return np.array(out, np.int64)
+
+
 def _find(metrics: DetectMetrics, hop, sf, osr, frame_symbols, sync, thresh_db, first, row_len, bw) -> np.ndarray:
     N, step, k, sw0, sw1, frame_len = _geometry(hop, sf, osr, frame_symbols, sync, bw)
     hop, osr = int(hop), step // N
@@ -80,27 +119,9 @@ def _find(metrics: DetectMetrics, hop, sf, osr, frame_symbols, sync, thresh_db, 
         row_len = (W - 1) * hop + step if W else 0
     if W <= k:
         return np.zeros(0, np.int64)
-    # the candidate mask and each candidate's refined start, on the tensors' device
-    ok = (power - floor) >= float(thresh_db)
-    idx = index.to(torch.int64)
-    n = W - k
-    cand = ok[:n] & ok[k:] & (torch.remainder(idx[k:] - idx[:n], N) == (sw1 - sw0) % N)
-    d = torch.remainder(idx[:n] - sw0, N)
-    d = torch.where(d >= N // 2, d - N, d)
-    start = torch.arange(n, dtype=torch.int64, device=power.device) * hop - d * osr
-    packed = torch.where(cand, start, torch.full_like(start, _NONE)).cpu().numpy()  # the one synchronisation
-    # the greedy pass, on the host, over the candidates only
-    first = int(first)
-    wmin = _ceil_div(max(first - step // 2, 0), hop)
-    out = []
-    for w in np.flatnonzero(packed != _NONE):
-        w, s = int(w), int(packed[w])
-        if w < wmin or s < first or s + frame_len > row_len:
-            continue
-        out.append(s)
-        first = s + frame_len
-        wmin = max(w + 1, _ceil_div(max(first - step // 2, 0), hop))
-    return np.array(out, np.int64)
+    packed = _candidates(power, floor, index, hop, N, osr, k, sw0, sw1, thresh_db)
+    packed = packed.cpu().numpy()  # the one synchronisation
+    return _greedy(packed, hop, step, frame_len, first, row_len)
 
 
 def find_frames(metrics: DetectMetrics, hop: int, sf: int, osr: int, frame_symbols: int, sync: int = 0x12,
@@ -171,11 +192,173 @@ def receive(plan: DemodPlan, iq: torch.Tensor, frame_symbols: int, hop: Optional
     K = len(starts)
     starts_t = torch.from_numpy(starts).to(dev)
     if K == 0:
-        return starts_t, DemodResult(symbols=torch.empty((0, int(frame_symbols)), dtype=torch.uint16, device=dev),
-                                     sync=torch.empty(0, dtype=torch.uint8, device=dev),
-                                     cfo=torch.empty(0, dtype=torch.float32, device=dev),
-                                     time_offset=torch.empty(0, dtype=torch.float32, device=dev),
-                                     max_amp=torch.empty(0, dtype=torch.float32, device=dev))
+        return starts_t, _no_frames(frame_symbols, dev)
     # (the finder only accepts frames that fit the stream, so the gather needs no second check)
     return starts_t, plan.run(_gather(iq, starts_t, frame_len))
+
+
+def _no_frames(frame_symbols: int, dev: torch.device) -> DemodResult:
+    return DemodResult(symbols=torch.empty((0, int(frame_symbols)), dtype=torch.uint16, device=dev),
+                       sync=torch.empty(0, dtype=torch.uint8, device=dev),
+                       cfo=torch.empty(0, dtype=torch.float32, device=dev),
+                       time_offset=torch.empty(0, dtype=torch.float32, device=dev),
+                       max_amp=torch.empty(0, dtype=torch.float32, device=dev))
+
+
+def lowpass_taps(ntaps: int, cutoff: float) -> np.ndarray:
+    """A Hamming-windowed sinc low-pass for ``Channelizer``: float32 [ntaps],
+    ``2*cutoff*sinc(2*cutoff*(j - (ntaps-1)/2)) * hamming(ntaps)`` computed in double, divided by
+    its sum (unit gain at the channel centre), then rounded to fp32.  ``cutoff`` is in cycles per
+    input sample, ``0 < cutoff <= 0.5``."""
+    ntaps, cutoff = int(ntaps), float(cutoff)
+    if ntaps < 1:
+        raise ValueError("ntaps must be >= 1")
+    if not 0.0 < cutoff <= 0.5:
+        raise ValueError("cutoff must be in (0, 0.5] cycles per sample")
+    j = np.arange(ntaps, dtype=np.float64)
+    h = 2.0 * cutoff * np.sinc(2.0 * cutoff * (j - (ntaps - 1) / 2.0)) * np.hamming(ntaps)
+    return (h / h.sum()).astype(np.float32)
+
+
+def nco_table(period: int) -> np.ndarray:
+    """The oscillator table ``Channelizer`` uses: ``exp(-2 pi i m / period)``, m = 0 .. period-1,
+    cosine and sine computed in double and rounded to fp32 (complex64 [period])."""
+    ang = -2.0 * np.pi * np.arange(int(period), dtype=np.float64) / int(period)
+    w = np.empty(int(period), np.complex64)
+    w.real = np.cos(ang).astype(np.float32)
+    w.imag = np.sin(ang).astype(np.float32)
+    return w
+
+
+class Channelizer:
+    """A digital down-converter bank on the GPU (lora_channelize_batch): one wideband stream in,
+    ``C = len(steps)`` channel streams out, each mixed down from ``steps[c] / period`` cycles per
+    input sample above the tuner, low-pass filtered with the real ``taps`` and decimated by
+    ``decim``.  One kernel reads the wideband data once.  The arithmetic is defined exactly in
+    include/lora_mi355x.h (the definition is this library's own: the reference has no
+    channelizer), so a host restatement reproduces every bit.
+
+    Limits: channel centres are multiples of ``fs / period``; the input rate must be
+    ``decim * bw * osr`` of the demodulator that follows (there is no rational resampling);
+    ``decim`` 1..64, 1..512 taps, ``period`` 1..4096, 1..32 channels.
+
+    The taps and the oscillator table (``nco_table(period)``) are kept on the device.
+    ``delay`` is the filter's group delay, ``(ntaps - 1) / 2`` input samples."""
+
+    def __init__(self, decim: int, taps, period: int, steps, device=None):
+        self.decim, self.period = int(decim), int(period)
+        h = np.ascontiguousarray(taps, np.float32)
+        self.steps = [int(k) for k in steps]
+        if not 1 <= self.decim <= 64:
+            raise ValueError("decim must be in 1..64")
+        if h.ndim != 1 or not 1 <= h.shape[0] <= 512:
+            raise ValueError("taps must be 1..512 real values")
+        if not 1 <= self.period <= 4096:
+            raise ValueError("period must be in 1..4096")
+        if not 1 <= len(self.steps) <= 32 or any(abs(k) >= 1 << 31 for k in self.steps):
+            raise ValueError("steps must be 1..32 ints")
+        self.ntaps, self.channels = int(h.shape[0]), len(self.steps)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise TypeError("Channelizer runs on a CUDA (HIP) device; there is no CPU fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._lib = _capi.lib()
+        self._steps = (_capi.C.c_int32 * self.channels)(*self.steps)
+        self.taps = torch.from_numpy(h.copy()).to(self.device)
+        self.nco = torch.from_numpy(nco_table(self.period)).to(self.device)
+
+    @property
+    def delay(self) -> float:
+        return (self.ntaps - 1) / 2
+
+    def outputs(self, L: int) -> int:
+        """Outputs per channel for a row of ``L`` samples: ``0 if L < ntaps else (L - ntaps) //
+        decim + 1`` (lora_channelize_outputs)."""
+        return _capi.check(self._lib.lora_channelize_outputs(int(L), self.ntaps, self.decim))
+
+    def run(self, iq: torch.Tensor, first_sample: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Channelize a [L] complex64 CUDA stream into [C, W], or [R, L] rows (a strided view with
+        non-overlapping rows is accepted, as for ``DemodPlan.scan``) into [R, C, W]; ``W =
+        outputs(L)``.  ``first_sample`` (>= 0) is the index of ``iq[.., 0]`` in the recording, which
+        keeps the oscillators' phase continuous across chunks: a chunk that starts at a multiple of
+        ``decim`` and overlaps its predecessor by ``ntaps - decim`` samples continues its outputs.
+        ``out``: a contiguous complex64 [C, >= W] (or [R, C, >= W]) tensor to write into; its
+        columns from W on are left alone and the [.., :W] view is returned.  One kernel on the
+        current stream, nothing allocated besides the output, so the call can be captured in a
+        HIP graph."""
+        one = isinstance(iq, torch.Tensor) and iq.dim() == 1
+        iq = _check_iq(iq, self.device)
+        R, L = iq.shape
+        first_sample = int(first_sample)
+        if first_sample < 0:
+            raise ValueError("first_sample must be >= 0")
+        W = 0 if L < self.ntaps else (L - self.ntaps) // self.decim + 1
+        C = self.channels
+        if out is None:
+            out = torch.empty((C, W) if one else (R, C, W), dtype=torch.complex64, device=self.device)
+        else:
+            _require_cuda(out, "out")
+            want = (C,) if one else (R, C)
+            if out.dtype != torch.complex64:
+                raise TypeError("out must be complex64")
+            if (out.device != self.device or out.dim() != len(want) + 1 or tuple(out.shape[:-1]) != want
+                    or out.shape[-1] < W or not out.is_contiguous()):
+                raise ValueError(f"out must be a contiguous complex64 {list(want) + ['>=%d' % W]} tensor on "
+                                 f"{self.device}")
+        if R == 0 or W == 0:
+            return out[..., :W]  # nothing to launch (and an empty tensor has no address to pass)
+        got = _capi.check(self._lib.lora_channelize_batch(
+            iq.data_ptr(), R, L, iq.stride(0) if R > 1 else L, first_sample, self.taps.data_ptr(), self.ntaps,
+            self.decim, self.nco.data_ptr(), self.period, self._steps, C, out.data_ptr(), out.shape[-1],
+            self.device.index, _stream_handle(self.device)))
+        assert got == W, (got, W)
+        return out[..., :W]
+
+
+def receive_wideband(plan: DemodPlan, chan: Channelizer, iq: torch.Tensor, frame_symbols: int,
+                     hop: Optional[int] = None, sync: int = 0x12,
+                     thresh_db: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, DemodResult]:
+    """``receive`` for a wideband capture: channelize the [L] complex64 CUDA stream ``iq`` with
+    ``chan``, scan all channel rows at once, find the frames of ``frame_symbols`` data symbols in
+    each row by the finder's rule, gather them and demodulate them.
+
+    Returns ``(channel, starts, result)``: int64 [K] tensors on the plan's device, ordered by
+    channel and then by start, and ``plan.run``'s DemodResult for the K frames.  Starts are in
+    CHANNEL samples: frame i began near wideband sample ``starts[i] * chan.decim + chan.delay``.
+
+    The plan's constraints are ``receive``'s (``dechirp=True``, bw 125 kHz).  Its ``step`` must
+    match the channel rate - the wideband rate must be ``chan.decim * bw * osr`` - which is the
+    caller's responsibility: nothing here can check it.  The work is one ``Channelizer.run``,
+    one ``plan.scan`` over the [C, W] rows, one gather and one ``plan.run``; the candidates of all
+    rows come to the host in one copy, so there is one synchronisation, as in ``receive``.  With
+    no frame found the tensors are empty and no demod call is made."""
+    if not plan.dechirp:
+        raise ValueError("receive_wideband needs a plan with dechirp=True: the finder reads dechirped peaks")
+    if not isinstance(iq, torch.Tensor) or iq.dim() != 1:
+        raise ValueError("receive_wideband takes one [L] stream")
+    if chan.device != plan.device:
+        raise ValueError(f"the channelizer is on {chan.device}, the plan is on {plan.device}")
+    hop = plan.step // 4 if hop is None else int(hop)
+    N, step, k, sw0, sw1, frame_len = _geometry(hop, plan.sf, plan.osr, frame_symbols, sync, plan.bw)
+    rows = chan.run(iq)  # [C, Wc]
+    C, Wc = rows.shape
+    dev = plan.device
+    found = []
+    if Wc >= step:  # (scan of shorter rows has no window)
+        met = plan.scan(rows, hop)
+        if met.power.shape[1] > k:
+            packed = _candidates(met.power, met.power_avg, met.index, hop, N, step // N, k, sw0, sw1, thresh_db)
+            packed = packed.cpu().numpy()  # the one synchronisation
+            found = [_greedy(packed[c], hop, step, frame_len, 0, Wc) for c in range(C)]
+    K = sum(len(s) for s in found)
+    if K == 0:
+        empty = torch.empty(0, dtype=torch.int64, device=dev)
+        return empty, empty.clone(), _no_frames(frame_symbols, dev)
+    channel = np.repeat(np.arange(C, dtype=np.int64), [len(s) for s in found])
+    starts = np.concatenate(found)
+    channel_t, starts_t = torch.from_numpy(channel).to(dev), torch.from_numpy(starts).to(dev)
+    # the rows are one contiguous [C * Wc] stream; the finder only accepts frames inside their row
+    frames = _gather(rows.reshape(-1), channel_t * Wc + starts_t, frame_len)
+    return channel_t, starts_t, plan.run(frames)
 
