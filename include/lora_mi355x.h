@@ -288,6 +288,46 @@ int64_t lora_channelize_batch(const float* iq, int64_t rows, int64_t row_len, in
                               const float* nco, int64_t period, const int32_t* steps, int64_t channels,
                               float* out, int64_t out_stride, int device, void* stream);
 
+/* Rational-rate down-converter bank: lora_channelize_batch with an interpolation factor, for a
+ * wideband rate that is decim / interp times the channel rate (2.4 MS/s to 125 kS/s is 5/96).
+ * The reference has no channelizer; this definition is the library's own.  The arguments are
+ * lora_channelize_batch's, plus `interp` (L); `decim` is M, and `taps` are `ntaps` real fp32
+ * values h[j] of a prototype filter at L times the input rate.
+ * Mixing is unchanged: for sample n of a row, m = (k_c * (first_sample + n)) mod period and
+ *   zr = xr*wr[m] - xi*wi[m]        zi = xr*wi[m] + xi*wr[m].
+ * Output t of a channel is the zero-stuffed correlation sum_j h[j] * zup[t*M + j], where
+ * zup[v] = z[v / L] when L divides v; the zero terms are left out, not added:
+ *   j0 = (-(t*M)) mod L, in 0 .. L-1;      n0 = (t*M + j0) / L;
+ *   K  = j0 >= ntaps ? 0 : ceil((ntaps - j0) / L);
+ * both accumulators start at +0.0f and, for i = 0 .. K-1 in this order,
+ *   yr = yr + h[j0 + i*L]*zr[n0 + i]    yi = yi + h[j0 + i*L]*zi[n0 + i].
+ * All arithmetic is fp32, one rounding per operation, no contraction.  A residue with K == 0
+ * gives (+0.0f, +0.0f).  Infinities and NaN propagate as this arithmetic makes them, with
+ * lora_channelize_batch's caveat about a NaN's sign and payload.
+ * A row gives, with span = (row_len - 1)*L + 1,
+ *   W = (row_len < 1 || span < ntaps) ? 0 : (span - ntaps) / M + 1
+ * outputs per channel, and no output reads past its row.  At interp == 1 every formula here is
+ * lora_channelize_batch's.
+ * Chunks: a chunk continues its predecessor's outputs when it starts at input sample n0 with
+ * n0 * L a multiple of M, is given first_sample = n0, and the predecessor is long enough to
+ * hold all outputs before n0*L/M.
+ *
+ * lora_resample_outputs: host arithmetic only; W, or LORA_EINVAL for a negative row_len,
+ * ntaps < 1, interp < 1, decim < 1 or a row_len * interp beyond 64 bits.
+ * lora_resample_channelize_batch: enqueues one kernel on `stream` of `device`, allocates and
+ * synchronises nothing, needs no workspace, and fully writes columns 0 .. W-1 of every (row,
+ * channel) and nothing beyond them.  rows == 0 or W == 0: no launch.  LORA_EINVAL, before any
+ * HIP call: lora_channelize_batch's argument rules with these limits - interp outside 1..16,
+ * decim outside 1..256, interp > decim (a rate-reducing bank only), ntaps outside 1..4096,
+ * ceil(ntaps / interp) > 512, period outside 1..4096, channels outside 1..32, row_len >= 2^31.
+ * (2.048 MS/s to 125 kS/s is 125/2048: beyond these limits.)  Returns W. */
+int64_t lora_resample_outputs(int64_t row_len, int64_t ntaps, int64_t interp, int64_t decim);
+int64_t lora_resample_channelize_batch(const float* iq, int64_t rows, int64_t row_len, int64_t row_stride,
+                                       int64_t first_sample, const float* taps, int64_t ntaps, int64_t interp,
+                                       int64_t decim, const float* nco, int64_t period, const int32_t* steps,
+                                       int64_t channels, float* out, int64_t out_stride, int device,
+                                       void* stream);
+
 /* lora_modulate for `frames` independent frames: symbols [frames][sym_count] ->
  * iq [frames][(sym_count+2)*N*osr] (2 sync up-chirps then one chirp per symbol,
  * phase-continuous within a frame, LoRaMod.cpp:8-41).  Returns samples per frame. */

@@ -41,6 +41,8 @@ EXPORTED_SYMBOLS = (
     "lora_detect_scan_batch",
     "lora_channelize_outputs",
     "lora_channelize_batch",
+    "lora_resample_outputs",
+    "lora_resample_channelize_batch",
     "lora_mod_batch",
     "lora_estimate_offsets_batch",
     "lora_compensate_offsets_batch",
@@ -149,6 +151,14 @@ def lib() -> C.CDLL:
     L.lora_channelize_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                         C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int32),
                                         C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    # the rational-rate bank (csrc/lora_resample.hip): interp goes before decim
+    L.lora_resample_outputs.restype = C.c_int64
+    L.lora_resample_outputs.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64]
+    L.lora_resample_channelize_batch.restype = C.c_int64
+    L.lora_resample_channelize_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                                 C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                 C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_void_p,
+                                                 C.c_int64, C.c_int, C.c_void_p]
     L.lora_mod_batch.restype = C.c_int64
     L.lora_mod_batch.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_float, C.c_uint8, C.c_void_p,
                                  C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]

@@ -499,7 +499,9 @@ class LoRaDemod:
         into its channel rows, whose frames are found and demodulated.  Returns ``(channel,
         starts, symbols[:, :mtu])`` - per frame its channel and the sample index, in channel
         samples, of its first sync symbol, ordered by channel then start; ``last`` keeps the
-        DemodResult of the K frames.  This block's ``osr`` and bw must be the channel rows'."""
+        DemodResult of the K frames.  Frame i began near wideband sample ``starts[i] * chan.decim /
+        chan.interp + chan.delay``.  This block's ``osr`` and bw must be the channel rows': the
+        wideband rate must be ``bw * osr * chan.decim / chan.interp``."""
         from . import stream
 
         channel, starts, res = stream.receive_wideband(self.plan, chan, iq, frame_symbols, hop, self.sync,

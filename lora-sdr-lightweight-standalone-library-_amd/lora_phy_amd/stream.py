@@ -39,8 +39,10 @@ kernel mixes every channel down, low-pass filters and decimates it (lora_channel
 exact arithmetic is in include/lora_mi355x.h and, like the finder's rule, is this project's own:
 the reference has no channelizer), and ``receive_wideband`` is ``receive`` over all the channel
 rows at once.  Channel centres are multiples of ``fs / period``; the input rate must be
-``decim * bw * osr`` (there is no rational resampling); the finder's 125 kHz restriction is
-inherited; and again no detection-probability figure is claimed.
+``bw * osr * decim / interp`` - an integer ``decim`` alone, or with ``interp > 1`` the rational
+bank (lora_resample_channelize_batch), whose ratios are those with ``interp <= 16`` and ``decim <=
+256`` (2.4 MS/s to 125 kS/s is 5/96; 2.048 MS/s, 125/2048, is beyond them); the finder's 125 kHz
+restriction is inherited; and again no detection-probability figure is claimed.
 """
 from __future__ import annotations
 
@@ -205,19 +207,22 @@ def _no_frames(frame_symbols: int, dev: torch.device) -> DemodResult:
                        max_amp=torch.empty(0, dtype=torch.float32, device=dev))
 
 
-def lowpass_taps(ntaps: int, cutoff: float) -> np.ndarray:
+def lowpass_taps(ntaps: int, cutoff: float, gain: float = 1.0) -> np.ndarray:
     """A Hamming-windowed sinc low-pass for ``Channelizer``: float32 [ntaps],
     ``2*cutoff*sinc(2*cutoff*(j - (ntaps-1)/2)) * hamming(ntaps)`` computed in double, divided by
-    its sum (unit gain at the channel centre), then rounded to fp32.  ``cutoff`` is in cycles per
-    input sample, ``0 < cutoff <= 0.5``."""
-    ntaps, cutoff = int(ntaps), float(cutoff)
+    its sum (unit gain at the channel centre) and multiplied by ``gain``, still in double, then
+    rounded to fp32.  ``cutoff`` is in cycles per sample of the rate the taps run at, ``0 < cutoff
+    <= 0.5``: the input rate, or for a rational bank ``interp`` times it - there ``gain=interp``
+    makes up for the zero-stuffing and ``cutoff`` is usually ``0.5 / decim``."""
+    ntaps, cutoff, gain = int(ntaps), float(cutoff), float(gain)
     if ntaps < 1:
         raise ValueError("ntaps must be >= 1")
     if not 0.0 < cutoff <= 0.5:
         raise ValueError("cutoff must be in (0, 0.5] cycles per sample")
     j = np.arange(ntaps, dtype=np.float64)
     h = 2.0 * cutoff * np.sinc(2.0 * cutoff * (j - (ntaps - 1) / 2.0)) * np.hamming(ntaps)
-    return (h / h.sum()).astype(np.float32)
+    h = h / h.sum()
+    return (h if gain == 1.0 else h * gain).astype(np.float32)
 
 
 def nco_table(period: int) -> np.ndarray:
@@ -231,28 +236,42 @@ def nco_table(period: int) -> np.ndarray:
 
 
 class Channelizer:
-    """A digital down-converter bank on the GPU (lora_channelize_batch): one wideband stream in,
-    ``C = len(steps)`` channel streams out, each mixed down from ``steps[c] / period`` cycles per
-    input sample above the tuner, low-pass filtered with the real ``taps`` and decimated by
-    ``decim``.  One kernel reads the wideband data once.  The arithmetic is defined exactly in
-    include/lora_mi355x.h (the definition is this library's own: the reference has no
-    channelizer), so a host restatement reproduces every bit.
+    """A digital down-converter bank on the GPU: one wideband stream in, ``C = len(steps)``
+    channel streams out, each mixed down from ``steps[c] / period`` cycles per input sample above
+    the tuner, low-pass filtered with the real ``taps`` and resampled by ``interp / decim``.  One
+    kernel reads the wideband data once.  With ``interp == 1`` it is lora_channelize_batch: the
+    taps run at the input rate and every ``decim``-th filter output is kept.  With ``interp > 1``
+    it is lora_resample_channelize_batch, the polyphase interpolate-by-``interp``,
+    decimate-by-``decim`` bank: the taps are a prototype filter at ``interp`` times the input rate
+    (``lowpass_taps(ntaps, 0.5 / decim, gain=interp)``).  The arithmetic of both is defined
+    exactly in include/lora_mi355x.h (the definitions are this library's own: the reference has
+    no channelizer), so a host restatement reproduces every bit.
 
-    Limits: channel centres are multiples of ``fs / period``; the input rate must be
-    ``decim * bw * osr`` of the demodulator that follows (there is no rational resampling);
-    ``decim`` 1..64, 1..512 taps, ``period`` 1..4096, 1..32 channels.
+    Limits: channel centres are multiples of ``fs / period``; the input rate must be ``bw * osr
+    * decim / interp`` of the demodulator that follows; ``period`` 1..4096, 1..32 channels; with
+    ``interp == 1`` ``decim`` 1..64 and 1..512 taps; with ``interp`` 2..16 ``decim`` ``interp``..256
+    (a rate-reducing bank only) and 1..4096 taps with ``ceil(ntaps / interp) <= 512``.  Ratios
+    beyond those (2.048 MS/s to 125 kS/s is 125/2048) are not covered.
 
     The taps and the oscillator table (``nco_table(period)``) are kept on the device.
-    ``delay`` is the filter's group delay, ``(ntaps - 1) / 2`` input samples."""
+    ``delay`` is the filter's group delay, ``(ntaps - 1) / (2 * interp)`` input samples."""
 
-    def __init__(self, decim: int, taps, period: int, steps, device=None):
-        self.decim, self.period = int(decim), int(period)
+    def __init__(self, decim: int, taps, period: int, steps, device=None, interp: int = 1):
+        self.decim, self.period, self.interp = int(decim), int(period), int(interp)
         h = np.ascontiguousarray(taps, np.float32)
         self.steps = [int(k) for k in steps]
-        if not 1 <= self.decim <= 64:
-            raise ValueError("decim must be in 1..64")
-        if h.ndim != 1 or not 1 <= h.shape[0] <= 512:
-            raise ValueError("taps must be 1..512 real values")
+        if not 1 <= self.interp <= 16:
+            raise ValueError("interp must be in 1..16")
+        if self.interp == 1:
+            if not 1 <= self.decim <= 64:
+                raise ValueError("decim must be in 1..64")
+            if h.ndim != 1 or not 1 <= h.shape[0] <= 512:
+                raise ValueError("taps must be 1..512 real values")
+        else:
+            if not self.interp <= self.decim <= 256:
+                raise ValueError("with interp > 1, decim must be in interp..256 (a rate-reducing bank only)")
+            if h.ndim != 1 or not 1 <= h.shape[0] <= 4096 or -(-h.shape[0] // self.interp) > 512:
+                raise ValueError("taps must be 1..4096 real values, at most 512 per interpolation phase")
         if not 1 <= self.period <= 4096:
             raise ValueError("period must be in 1..4096")
         if not 1 <= len(self.steps) <= 32 or any(abs(k) >= 1 << 31 for k in self.steps):
@@ -270,19 +289,32 @@ class Channelizer:
 
     @property
     def delay(self) -> float:
-        return (self.ntaps - 1) / 2
+        return (self.ntaps - 1) / (2 * self.interp)
+
+    def _outputs(self, L: int) -> int:
+        if self.interp == 1:
+            return 0 if L < self.ntaps else (L - self.ntaps) // self.decim + 1
+        span = (L - 1) * self.interp + 1
+        return 0 if L < 1 or span < self.ntaps else (span - self.ntaps) // self.decim + 1
 
     def outputs(self, L: int) -> int:
-        """Outputs per channel for a row of ``L`` samples: ``0 if L < ntaps else (L - ntaps) //
-        decim + 1`` (lora_channelize_outputs)."""
-        return _capi.check(self._lib.lora_channelize_outputs(int(L), self.ntaps, self.decim))
+        """Outputs per channel for a row of ``L`` samples.  ``interp == 1``: ``0 if L < ntaps else
+        (L - ntaps) // decim + 1`` (lora_channelize_outputs).  Otherwise, with ``span = (L - 1) *
+        interp + 1``: ``0 if L < 1 or span < ntaps else (span - ntaps) // decim + 1``
+        (lora_resample_outputs)."""
+        if self.interp == 1:
+            return _capi.check(self._lib.lora_channelize_outputs(int(L), self.ntaps, self.decim))
+        return _capi.check(self._lib.lora_resample_outputs(int(L), self.ntaps, self.interp, self.decim))
 
     def run(self, iq: torch.Tensor, first_sample: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Channelize a [L] complex64 CUDA stream into [C, W], or [R, L] rows (a strided view with
         non-overlapping rows is accepted, as for ``DemodPlan.scan``) into [R, C, W]; ``W =
         outputs(L)``.  ``first_sample`` (>= 0) is the index of ``iq[.., 0]`` in the recording, which
         keeps the oscillators' phase continuous across chunks: a chunk that starts at a multiple of
-        ``decim`` and overlaps its predecessor by ``ntaps - decim`` samples continues its outputs.
+        ``decim`` and overlaps its predecessor by ``ntaps - decim`` samples continues its outputs
+        (with ``interp > 1``: a chunk that starts at a sample ``n0`` with ``n0 * interp`` a multiple
+        of ``decim``, after a predecessor long enough to hold the ``n0 * interp / decim`` outputs
+        before it).
         ``out``: a contiguous complex64 [C, >= W] (or [R, C, >= W]) tensor to write into; its
         columns from W on are left alone and the [.., :W] view is returned.  One kernel on the
         current stream, nothing allocated besides the output, so the call can be captured in a
@@ -293,7 +325,7 @@ class Channelizer:
         first_sample = int(first_sample)
         if first_sample < 0:
             raise ValueError("first_sample must be >= 0")
-        W = 0 if L < self.ntaps else (L - self.ntaps) // self.decim + 1
+        W = self._outputs(L)
         C = self.channels
         if out is None:
             out = torch.empty((C, W) if one else (R, C, W), dtype=torch.complex64, device=self.device)
@@ -308,9 +340,12 @@ class Channelizer:
                                  f"{self.device}")
         if R == 0 or W == 0:
             return out[..., :W]  # nothing to launch (and an empty tensor has no address to pass)
-        got = _capi.check(self._lib.lora_channelize_batch(
+        # the rational entry is the integer one with interp in front of decim
+        entry, rates = ((self._lib.lora_channelize_batch, (self.decim,)) if self.interp == 1 else
+                        (self._lib.lora_resample_channelize_batch, (self.interp, self.decim)))
+        got = _capi.check(entry(
             iq.data_ptr(), R, L, iq.stride(0) if R > 1 else L, first_sample, self.taps.data_ptr(), self.ntaps,
-            self.decim, self.nco.data_ptr(), self.period, self._steps, C, out.data_ptr(), out.shape[-1],
+            *rates, self.nco.data_ptr(), self.period, self._steps, C, out.data_ptr(), out.shape[-1],
             self.device.index, _stream_handle(self.device)))
         assert got == W, (got, W)
         return out[..., :W]
@@ -325,12 +360,13 @@ def receive_wideband(plan: DemodPlan, chan: Channelizer, iq: torch.Tensor, frame
 
     Returns ``(channel, starts, result)``: int64 [K] tensors on the plan's device, ordered by
     channel and then by start, and ``plan.run``'s DemodResult for the K frames.  Starts are in
-    CHANNEL samples: frame i began near wideband sample ``starts[i] * chan.decim + chan.delay``.
+    CHANNEL samples: frame i began near wideband sample ``starts[i] * chan.decim / chan.interp +
+    chan.delay``.
 
     The plan's constraints are ``receive``'s (``dechirp=True``, bw 125 kHz).  Its ``step`` must
-    match the channel rate - the wideband rate must be ``chan.decim * bw * osr`` - which is the
-    caller's responsibility: nothing here can check it.  The work is one ``Channelizer.run``,
-    one ``plan.scan`` over the [C, W] rows, one gather and one ``plan.run``; the candidates of all
+    match the channel rate - the wideband rate must be ``bw * osr * chan.decim / chan.interp`` -
+    which is the caller's responsibility: nothing here can check it.  The work is one
+    ``Channelizer.run``, one ``plan.scan`` over the [C, W] rows, one gather and one ``plan.run``; the candidates of all
     rows come to the host in one copy, so there is one synchronisation, as in ``receive``.  With
     no frame found the tensors are empty and no demod call is made."""
     if not plan.dechirp:
