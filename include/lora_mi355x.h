@@ -328,6 +328,50 @@ int64_t lora_resample_channelize_batch(const float* iq, int64_t rows, int64_t ro
                                        int64_t channels, float* out, int64_t out_stride, int device,
                                        void* stream);
 
+/* Raw SDR samples: both banks reading the capture as the radio wrote it, so that the integer
+ * bytes are the only read of it (no convert pass, no workspace, no second kernel).  `format`
+ * is one of */
+#define LORA_IQ_CS16 1 /* little-endian int16 I, Q: 4 bytes per sample (USRP, Pluto, LimeSDR, .sigmf-data) */
+#define LORA_IQ_CS8 2  /* int8 I, Q: 2 bytes per sample (HackRF) */
+#define LORA_IQ_CU8 3  /* uint8 I, Q: 2 bytes per sample (RTL-SDR) */
+/* The reference has no channelizer; this definition, like the banks', is the library's own.
+ * For a stored component v, the fp32 sample component is
+ *   x = ((float)v - bias) * scale
+ * all of it fp32, one rounding per operation, no contraction: the conversion of the integer is
+ * exact, bias is 127.5f for cu8 (the subtraction is exact too) and +0.0f for the signed formats,
+ * where the subtraction changes no bit and is left out, and the product is the one rounding.
+ * `scale` is the caller's fp32 value and is not checked: infinities and NaN propagate as the
+ * arithmetic makes them (scale = inf turns a zero component into NaN).  The usual scales are
+ * 1/32768, 1/128 and 1/127.5.  xr and xi then enter the float entry's mixing and FIR formulas
+ * unchanged, so the outputs equal, bit for bit, the float entry's on the converted samples.
+ *
+ * lora_channelize_raw_batch is lora_channelize_batch and lora_resample_channelize_raw_batch is
+ * lora_resample_channelize_batch, argument for argument, limit for limit and rule for rule, with
+ * `const void* iq, int format, float scale` in place of `const float* iq`:
+ *   iq    `rows` rows of `row_len` samples of `format`; row r begins r*row_stride SAMPLES after
+ *         iq (device).  row_stride, row_len and first_sample stay in complex samples.  iq need
+ *         only be aligned to one sample - 4 bytes for cs16, 2 bytes for cs8 and cu8 - so any
+ *         sample of a capture can be a row's first; the kernel loads two samples at a time on
+ *         the grid of that size (8 bytes for cs16, 4 for cs8 and cu8) and loads singly the one
+ *         sample that may hang over either end.
+ * W (lora_channelize_outputs, lora_resample_outputs: they serve both), the output layout, the
+ * chunking rule, graph capturability and the contract - one kernel on `stream` of `device`,
+ * nothing allocated or synchronised, no workspace, columns 0 .. W-1 fully written and nothing
+ * beyond them, rows == 0 or W == 0 no launch (and a NULL iq allowed) - are the float entries'.
+ * LORA_EINVAL, before any HIP call: a `format` that is none of the three (0 included), an iq
+ * that is not aligned to one sample, and every argument rule of the float counterpart.
+ * Returns W.  Nothing here corrects what an SDR front end does to the samples (DC offset, IQ
+ * imbalance): the conversion above is the whole of it. */
+int64_t lora_channelize_raw_batch(const void* iq, int format, float scale, int64_t rows, int64_t row_len,
+                                  int64_t row_stride, int64_t first_sample, const float* taps, int64_t ntaps,
+                                  int64_t decim, const float* nco, int64_t period, const int32_t* steps,
+                                  int64_t channels, float* out, int64_t out_stride, int device, void* stream);
+int64_t lora_resample_channelize_raw_batch(const void* iq, int format, float scale, int64_t rows, int64_t row_len,
+                                           int64_t row_stride, int64_t first_sample, const float* taps,
+                                           int64_t ntaps, int64_t interp, int64_t decim, const float* nco,
+                                           int64_t period, const int32_t* steps, int64_t channels, float* out,
+                                           int64_t out_stride, int device, void* stream);
+
 /* lora_modulate for `frames` independent frames: symbols [frames][sym_count] ->
  * iq [frames][(sym_count+2)*N*osr] (2 sync up-chirps then one chirp per symbol,
  * phase-continuous within a frame, LoRaMod.cpp:8-41).  Returns samples per frame. */

@@ -18,6 +18,10 @@
 // otherwise it shrinks to 32, 16 or 8, and if the channels still do not fit they are taken in
 // passes of `cg`, each pass re-reading the tile's samples (the ABI's extremes, 32 channels of
 // 512 taps at decim 64, run that way).
+//
+// The kernel is a template over the sample format (csrc/lora_iq_format.h): complex64 for
+// lora_channelize_batch, cs16, cs8 and cu8 for lora_channelize_raw_batch, whose integer samples
+// become fp32 in the load in front of the mixing and are otherwise the same kernel's.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -25,6 +29,7 @@
 #include "../../include/lora_mi355x.h"
 #include "lora_device.h"
 #include "lora_internal.h"
+#include "lora_iq_format.h"
 
 #pragma clang fp contract(off)
 
@@ -37,7 +42,7 @@ constexpr int kLdsSamples = 8192;  // mixed samples a workgroup holds: 64 KiB
 constexpr int kMaxTaps = 512, kMaxDecim = 64, kMaxPeriod = 4096, kMaxChannels = 32;
 
 struct ChanArgs {
-  const cf* iq;
+  const void* iq;  // samples of the kernel's format
   const float* taps;
   const cf* nco;
   cf* out;
@@ -47,6 +52,7 @@ struct ChanArgs {
   int tile, lg_tile, ps, cg;
   float inv_decim, inv_period;
   int steps[kMaxChannels];  // each in 0 .. period-1
+  float scale;              // of an integer format's samples
 };
 
 // LDS entries of one channel: decim phase rows of `tile` outputs plus the taps' reach
@@ -71,6 +77,7 @@ __device__ __forceinline__ void divmod(unsigned a, unsigned d, float inv, unsign
   r = (unsigned)rr;
 }
 
+template <int F>
 __global__ void __launch_bounds__(kThreads) k_channelize(ChanArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   v2f* Z = reinterpret_cast<v2f*>(smem);  // [cg][decim][ps]
@@ -81,7 +88,6 @@ __global__ void __launch_bounds__(kThreads) k_channelize(ChanArgs a) {
   // the tile's first sample and how many it covers; the last output's window ends inside the
   // row ((W-1)*decim + ntaps <= row_len), so nothing below reads past it
   const int64_t n0 = t0 * a.decim;  // < row_len < 2^31
-  const cf* x = a.iq + row * a.row_stride + n0;
   const int cnt = (nv - 1) * a.decim + a.ntaps;
   const int chs = channel_entries(a.tile, a.ntaps, a.decim);
   // the oscillator's position at the tile's first sample: (first_sample + n0) mod period
@@ -111,21 +117,9 @@ __global__ void __launch_bounds__(kThreads) k_channelize(ChanArgs a) {
         dst[c * chs] = z;
       }
     };
-    // pairs on the 16-byte grid of the address space: pair q holds samples 2q - mis and
-    // 2q + 1 - mis; a pair that hangs over either end is loaded singly
-    const int mis = (int)((reinterpret_cast<uintptr_t>(x) >> 3) & 1);
-    const int pairs = (cnt + mis + 1) >> 1;
-    for (int q = tid; q < pairs; q += kThreads) {
-      const int s0 = 2 * q - mis;
-      if (s0 >= 0 && s0 + 1 < cnt) {
-        const float4 v = *reinterpret_cast<const float4*>(x + s0);
-        mix(s0, v.x, v.y);
-        mix(s0 + 1, v.z, v.w);
-      } else {
-        if (s0 >= 0) mix(s0, x[s0].re, x[s0].im);
-        if (s0 + 1 < cnt) mix(s0 + 1, x[s0 + 1].re, x[s0 + 1].im);
-      }
-    }
+    // pairs of samples on the grid of a pair's size (16 bytes of complex64); a pair that hangs
+    // over either end of the tile's samples is loaded singly
+    load_samples<F>(a.iq, row * a.row_stride + n0, cnt, a.scale, tid, kThreads, mix);
     __syncthreads();
 
     // output t0 + tl of channels c and c + ncl: tap j meets sample tl * decim + j, entry
@@ -174,24 +168,11 @@ void channel_geometry(int ntaps, int decim, int channels, int& tile, int& cg) {
   if (cg > channels) cg = channels;
 }
 
-}  // namespace
-}  // namespace lora
-
-using lora::set_last_error;
-
-extern "C" {
-
-int64_t lora_channelize_outputs(int64_t row_len, int64_t ntaps, int64_t decim) {
-  if (row_len < 0 || ntaps < 1 || decim < 1)
-    return set_last_error(LORA_EINVAL, "row_len must be >= 0, ntaps >= 1 and decim >= 1");
-  return lora::channel_outputs(row_len, ntaps, decim);
-}
-
-int64_t lora_channelize_batch(const float* iq, int64_t rows, int64_t row_len, int64_t row_stride,
-                              int64_t first_sample, const float* taps, int64_t ntaps, int64_t decim,
-                              const float* nco, int64_t period, const int32_t* steps, int64_t channels,
-                              float* out, int64_t out_stride, int device, void* stream) {
-  using namespace lora;
+// Both entries: `format` is kIqCf32 for lora_channelize_batch, else a checked LORA_IQ_*
+int64_t channelize(const void* iq, int format, float scale, int64_t rows, int64_t row_len, int64_t row_stride,
+                   int64_t first_sample, const float* taps, int64_t ntaps, int64_t decim, const float* nco,
+                   int64_t period, const int32_t* steps, int64_t channels, float* out, int64_t out_stride,
+                   int device, void* stream) {
   if (!taps || !nco || !steps || !out) return set_last_error(LORA_EINVAL, "null taps / nco / steps / out");
   if (rows < 0 || row_len < 0 || row_stride < 0 || out_stride < 0 || first_sample < 0)
     return set_last_error(LORA_EINVAL, "negative rows / row_len / row_stride / out_stride / first_sample");
@@ -213,7 +194,8 @@ int64_t lora_channelize_batch(const float* iq, int64_t rows, int64_t row_len, in
     return set_last_error(LORA_EINVAL, "batch too large");
   if (rows == 0 || W == 0) return W;
   if (!iq) return set_last_error(LORA_EINVAL, "null iq");
-  a.iq = reinterpret_cast<const cf*>(iq);
+  a.iq = iq;
+  a.scale = scale;
   a.taps = taps;
   a.nco = reinterpret_cast<const cf*>(nco);
   a.out = reinterpret_cast<cf*>(out);
@@ -238,12 +220,46 @@ int64_t lora_channelize_batch(const float* iq, int64_t rows, int64_t row_len, in
   hipError_t e = hipGetDevice(&prev);
   if (e == hipSuccess && prev != device) e = hipSetDevice(device);
   if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("channelize device: ") + hipGetErrorString(e));
-  hipLaunchKernelGGL(k_channelize, dim3((unsigned)(rows * a.gpr)), dim3(kThreads), lds,
-                     static_cast<hipStream_t>(stream), a);
+  void (*const kernel)(ChanArgs) = format == LORA_IQ_CS16  ? k_channelize<LORA_IQ_CS16>
+                                   : format == LORA_IQ_CS8 ? k_channelize<LORA_IQ_CS8>
+                                   : format == LORA_IQ_CU8 ? k_channelize<LORA_IQ_CU8>
+                                                           : k_channelize<kIqCf32>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(rows * a.gpr)), dim3(kThreads), lds, static_cast<hipStream_t>(stream),
+                     a);
   e = hipGetLastError();
   if (prev != device) hipSetDevice(prev);
   if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("k_channelize: ") + hipGetErrorString(e));
   return W;
+}
+
+}  // namespace
+}  // namespace lora
+
+using lora::set_last_error;
+
+extern "C" {
+
+int64_t lora_channelize_outputs(int64_t row_len, int64_t ntaps, int64_t decim) {
+  if (row_len < 0 || ntaps < 1 || decim < 1)
+    return set_last_error(LORA_EINVAL, "row_len must be >= 0, ntaps >= 1 and decim >= 1");
+  return lora::channel_outputs(row_len, ntaps, decim);
+}
+
+int64_t lora_channelize_batch(const float* iq, int64_t rows, int64_t row_len, int64_t row_stride,
+                              int64_t first_sample, const float* taps, int64_t ntaps, int64_t decim,
+                              const float* nco, int64_t period, const int32_t* steps, int64_t channels,
+                              float* out, int64_t out_stride, int device, void* stream) {
+  return lora::channelize(iq, lora::kIqCf32, 0.0f, rows, row_len, row_stride, first_sample, taps, ntaps, decim, nco,
+                          period, steps, channels, out, out_stride, device, stream);
+}
+
+int64_t lora_channelize_raw_batch(const void* iq, int format, float scale, int64_t rows, int64_t row_len,
+                                  int64_t row_stride, int64_t first_sample, const float* taps, int64_t ntaps,
+                                  int64_t decim, const float* nco, int64_t period, const int32_t* steps,
+                                  int64_t channels, float* out, int64_t out_stride, int device, void* stream) {
+  if (const char* bad = lora::raw_format_error(iq, format)) return set_last_error(LORA_EINVAL, bad);
+  return lora::channelize(iq, format, scale, rows, row_len, row_stride, first_sample, taps, ntaps, decim, nco, period,
+                          steps, channels, out, out_stride, device, stream);
 }
 
 }  // extern "C"

@@ -32,6 +32,12 @@
 // the fewest with which the items = interp * ceil(cg / (2 * 64 / tile)) of a full pass take the
 // fewest rounds, ceil(items / wavefronts) (5 wavefronts for interp 5 with one channel group,
 // where 4 would leave three of them idle while the first does a second residue).
+//
+// The kernel's body is a template over the sample format (csrc/lora_iq_format.h):
+// k_channelize_resample is its complex64 instance, for lora_resample_channelize_batch, and
+// k_channelize_raw_resample<format> its cs16, cs8 and cu8 instances, for
+// lora_resample_channelize_raw_batch, whose integer samples become fp32 in the load in front of
+// the mixing.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -39,6 +45,7 @@
 #include "../../include/lora_mi355x.h"
 #include "lora_device.h"
 #include "lora_internal.h"
+#include "lora_iq_format.h"
 
 #pragma clang fp contract(off)
 
@@ -52,7 +59,7 @@ constexpr int kMaxInterp = 16, kMaxDecim = 256, kMaxTaps = 4096, kMaxPhaseTaps =
 constexpr int kMaxPeriod = 4096, kMaxChannels = 32;
 
 struct ResArgs {
-  const cf* iq;
+  const void* iq;  // samples of the kernel's format
   const float* taps;
   const cf* nco;
   cf* out;
@@ -64,6 +71,7 @@ struct ResArgs {
   int steps[kMaxChannels];  // each in 0 .. period-1
   // residue r = t mod interp: first tap, first sample past u*decim, taps
   int j0[kMaxInterp], off[kMaxInterp], K[kMaxInterp];
+  float scale;  // of an integer format's samples
 };
 
 __host__ __device__ constexpr int channel_entries(int tile, int reach, int decim) {
@@ -85,7 +93,8 @@ __device__ __forceinline__ void divmod(unsigned a, unsigned d, float inv, unsign
   r = (unsigned)rr;
 }
 
-__global__ void __launch_bounds__(kMaxThreads) k_channelize_resample(ResArgs a) {
+template <int F>
+__device__ __forceinline__ void resample_tile(const ResArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   v2f* Z = reinterpret_cast<v2f*>(smem);  // [cg][decim][ps]
   const int tid = threadIdx.x;
@@ -98,7 +107,6 @@ __global__ void __launch_bounds__(kMaxThreads) k_channelize_resample(ResArgs a) 
   // ((W-1)*decim + ntaps <= (row_len-1)*interp + 1); and no further than reach - 1 past its
   // u*decim, so cnt <= (tile-1)*decim + reach: every s below has its entry in Z.
   const int64_t n0 = u0 * a.decim;  // < row_len < 2^31
-  const cf* x = a.iq + row * a.row_stride + n0;
   const int cnt = (int)(((tend - 1) * a.decim + a.ntaps - 1) / a.interp - n0) + 1;
   const int chs = a.decim * a.ps;
   // the oscillator's position at the tile's first sample: (first_sample + n0) mod period
@@ -129,21 +137,9 @@ __global__ void __launch_bounds__(kMaxThreads) k_channelize_resample(ResArgs a) 
         dst[c * chs] = z;
       }
     };
-    // pairs on the 16-byte grid of the address space: pair q holds samples 2q - mis and
-    // 2q + 1 - mis; a pair that hangs over either end is loaded singly
-    const int mis = (int)((reinterpret_cast<uintptr_t>(x) >> 3) & 1);
-    const int pairs = (cnt + mis + 1) >> 1;
-    for (int q = tid; q < pairs; q += a.threads) {
-      const int s0 = 2 * q - mis;
-      if (s0 >= 0 && s0 + 1 < cnt) {
-        const float4 v = *reinterpret_cast<const float4*>(x + s0);
-        mix(s0, v.x, v.y);
-        mix(s0 + 1, v.z, v.w);
-      } else {
-        if (s0 >= 0) mix(s0, x[s0].re, x[s0].im);
-        if (s0 + 1 < cnt) mix(s0 + 1, x[s0 + 1].re, x[s0 + 1].im);
-      }
-    }
+    // pairs of samples on the grid of a pair's size (16 bytes of complex64); a pair that hangs
+    // over either end of the tile's samples is loaded singly
+    load_samples<F>(a.iq, row * a.row_stride + n0, cnt, a.scale, tid, a.threads, mix);
     __syncthreads();
 
     // output t0 + ul*interp + r of channels c and c + ncl: tap i of residue r meets sample
@@ -197,6 +193,13 @@ __global__ void __launch_bounds__(kMaxThreads) k_channelize_resample(ResArgs a) 
   }
 }
 
+__global__ void __launch_bounds__(kMaxThreads) k_channelize_resample(ResArgs a) { resample_tile<kIqCf32>(a); }
+
+template <int F>
+__global__ void __launch_bounds__(kMaxThreads) k_channelize_raw_resample(ResArgs a) {
+  resample_tile<F>(a);
+}
+
 int64_t resample_outputs(int64_t row_len, int64_t ntaps, int64_t interp, int64_t decim) {
   if (row_len < 1) return 0;
   const int64_t span = (row_len - 1) * interp + 1;
@@ -227,26 +230,11 @@ void resample_geometry(int reach, int interp, int decim, int channels, int& tile
     if ((items + w - 1) / w < (items + waves - 1) / waves) waves = w;
 }
 
-}  // namespace
-}  // namespace lora
-
-using lora::set_last_error;
-
-extern "C" {
-
-int64_t lora_resample_outputs(int64_t row_len, int64_t ntaps, int64_t interp, int64_t decim) {
-  if (row_len < 0 || ntaps < 1 || interp < 1 || decim < 1)
-    return set_last_error(LORA_EINVAL, "row_len must be >= 0, ntaps >= 1, interp >= 1 and decim >= 1");
-  if (row_len > INT64_MAX / interp) return set_last_error(LORA_EINVAL, "row_len * interp overflows");
-  return lora::resample_outputs(row_len, ntaps, interp, decim);
-}
-
-int64_t lora_resample_channelize_batch(const float* iq, int64_t rows, int64_t row_len, int64_t row_stride,
-                                       int64_t first_sample, const float* taps, int64_t ntaps, int64_t interp,
-                                       int64_t decim, const float* nco, int64_t period, const int32_t* steps,
-                                       int64_t channels, float* out, int64_t out_stride, int device,
-                                       void* stream) {
-  using namespace lora;
+// Both entries: `format` is kIqCf32 for lora_resample_channelize_batch, else a checked LORA_IQ_*
+int64_t resample_channelize(const void* iq, int format, float scale, int64_t rows, int64_t row_len,
+                            int64_t row_stride, int64_t first_sample, const float* taps, int64_t ntaps,
+                            int64_t interp, int64_t decim, const float* nco, int64_t period, const int32_t* steps,
+                            int64_t channels, float* out, int64_t out_stride, int device, void* stream) {
   if (!taps || !nco || !steps || !out) return set_last_error(LORA_EINVAL, "null taps / nco / steps / out");
   if (rows < 0 || row_len < 0 || row_stride < 0 || out_stride < 0 || first_sample < 0)
     return set_last_error(LORA_EINVAL, "negative rows / row_len / row_stride / out_stride / first_sample");
@@ -275,7 +263,8 @@ int64_t lora_resample_channelize_batch(const float* iq, int64_t rows, int64_t ro
     return set_last_error(LORA_EINVAL, "batch too large");
   if (rows == 0 || W == 0) return W;
   if (!iq) return set_last_error(LORA_EINVAL, "null iq");
-  a.iq = reinterpret_cast<const cf*>(iq);
+  a.iq = iq;
+  a.scale = scale;
   a.taps = taps;
   a.nco = reinterpret_cast<const cf*>(nco);
   a.out = reinterpret_cast<cf*>(out);
@@ -301,13 +290,50 @@ int64_t lora_resample_channelize_batch(const float* iq, int64_t rows, int64_t ro
   hipError_t e = hipGetDevice(&prev);
   if (e == hipSuccess && prev != device) e = hipSetDevice(device);
   if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("resample device: ") + hipGetErrorString(e));
-  hipLaunchKernelGGL(k_channelize_resample, dim3((unsigned)(rows * a.gpr)), dim3((unsigned)a.threads), lds,
+  void (*const kernel)(ResArgs) = format == LORA_IQ_CS16  ? k_channelize_raw_resample<LORA_IQ_CS16>
+                                  : format == LORA_IQ_CS8 ? k_channelize_raw_resample<LORA_IQ_CS8>
+                                  : format == LORA_IQ_CU8 ? k_channelize_raw_resample<LORA_IQ_CU8>
+                                                          : k_channelize_resample;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(rows * a.gpr)), dim3((unsigned)a.threads), lds,
                      static_cast<hipStream_t>(stream), a);
   e = hipGetLastError();
   if (prev != device) hipSetDevice(prev);
   if (e != hipSuccess)
     return set_last_error(LORA_EIO, std::string("k_channelize_resample: ") + hipGetErrorString(e));
   return W;
+}
+
+}  // namespace
+}  // namespace lora
+
+using lora::set_last_error;
+
+extern "C" {
+
+int64_t lora_resample_outputs(int64_t row_len, int64_t ntaps, int64_t interp, int64_t decim) {
+  if (row_len < 0 || ntaps < 1 || interp < 1 || decim < 1)
+    return set_last_error(LORA_EINVAL, "row_len must be >= 0, ntaps >= 1, interp >= 1 and decim >= 1");
+  if (row_len > INT64_MAX / interp) return set_last_error(LORA_EINVAL, "row_len * interp overflows");
+  return lora::resample_outputs(row_len, ntaps, interp, decim);
+}
+
+int64_t lora_resample_channelize_batch(const float* iq, int64_t rows, int64_t row_len, int64_t row_stride,
+                                       int64_t first_sample, const float* taps, int64_t ntaps, int64_t interp,
+                                       int64_t decim, const float* nco, int64_t period, const int32_t* steps,
+                                       int64_t channels, float* out, int64_t out_stride, int device,
+                                       void* stream) {
+  return lora::resample_channelize(iq, lora::kIqCf32, 0.0f, rows, row_len, row_stride, first_sample, taps, ntaps,
+                                   interp, decim, nco, period, steps, channels, out, out_stride, device, stream);
+}
+
+int64_t lora_resample_channelize_raw_batch(const void* iq, int format, float scale, int64_t rows, int64_t row_len,
+                                           int64_t row_stride, int64_t first_sample, const float* taps,
+                                           int64_t ntaps, int64_t interp, int64_t decim, const float* nco,
+                                           int64_t period, const int32_t* steps, int64_t channels, float* out,
+                                           int64_t out_stride, int device, void* stream) {
+  if (const char* bad = lora::raw_format_error(iq, format)) return set_last_error(LORA_EINVAL, bad);
+  return lora::resample_channelize(iq, format, scale, rows, row_len, row_stride, first_sample, taps, ntaps, interp,
+                                   decim, nco, period, steps, channels, out, out_stride, device, stream);
 }
 
 }  // extern "C"

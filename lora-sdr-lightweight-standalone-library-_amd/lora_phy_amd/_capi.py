@@ -24,6 +24,10 @@ LORA_WINDOW_HANN = 1
 LORA_MODE_LEGACY = 0
 LORA_MODE_API = 1
 LORA_MODE_RAW = 2
+# raw sample formats of the banks' raw entries (int16, int8, uint8 I, Q pairs)
+LORA_IQ_CS16 = 1
+LORA_IQ_CS8 = 2
+LORA_IQ_CU8 = 3
 
 # lora_demod_last_kernels bits
 KERNEL_BITS = {"frame_max": 1, "estimate": 2, "demod": 4, "generic": 16, "frame_max_wave": 32, "spec": 64}
@@ -43,6 +47,8 @@ EXPORTED_SYMBOLS = (
     "lora_channelize_batch",
     "lora_resample_outputs",
     "lora_resample_channelize_batch",
+    "lora_channelize_raw_batch",
+    "lora_resample_channelize_raw_batch",
     "lora_mod_batch",
     "lora_estimate_offsets_batch",
     "lora_compensate_offsets_batch",
@@ -159,6 +165,12 @@ def lib() -> C.CDLL:
                                                  C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                                  C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_void_p,
                                                  C.c_int64, C.c_int, C.c_void_p]
+    # the raw entries: their float counterparts with (iq, format, scale) in place of iq
+    L.lora_channelize_raw_batch.restype = C.c_int64
+    L.lora_channelize_raw_batch.argtypes = [C.c_void_p, C.c_int, C.c_float] + L.lora_channelize_batch.argtypes[1:]
+    L.lora_resample_channelize_raw_batch.restype = C.c_int64
+    L.lora_resample_channelize_raw_batch.argtypes = ([C.c_void_p, C.c_int, C.c_float] +
+                                                     L.lora_resample_channelize_batch.argtypes[1:])
     L.lora_mod_batch.restype = C.c_int64
     L.lora_mod_batch.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_float, C.c_uint8, C.c_void_p,
                                  C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]

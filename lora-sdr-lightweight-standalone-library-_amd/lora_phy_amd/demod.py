@@ -493,10 +493,10 @@ class LoRaDemod:
         return starts, res.symbols[:, :self.mtu]
 
     def work_wideband(self, chan, iq: torch.Tensor, frame_symbols: int, hop: Optional[int] = None,
-                      thresh_db: float = 0.0):
+                      thresh_db: float = 0.0, scale: Optional[float] = None):
         """``work_stream`` for a wideband capture (``lora_phy_amd.stream.receive_wideband`` with
         this block's plan and sync word): ``chan``, a ``stream.Channelizer``, turns the [L] stream
-        into its channel rows, whose frames are found and demodulated.  Returns ``(channel,
+        (complex64, or raw [L, 2] integer samples converted with ``scale``) into its channel rows, whose frames are found and demodulated.  Returns ``(channel,
         starts, symbols[:, :mtu])`` - per frame its channel and the sample index, in channel
         samples, of its first sync symbol, ordered by channel then start; ``last`` keeps the
         DemodResult of the K frames.  Frame i began near wideband sample ``starts[i] * chan.decim /
@@ -505,7 +505,7 @@ class LoRaDemod:
         from . import stream
 
         channel, starts, res = stream.receive_wideband(self.plan, chan, iq, frame_symbols, hop, self.sync,
-                                                       thresh_db)
+                                                       thresh_db, scale)
         self.last = res
         return channel, starts, res.symbols[:, :self.mtu]
 

@@ -43,6 +43,22 @@ rows at once.  Channel centres are multiples of ``fs / period``; the input rate 
 bank (lora_resample_channelize_batch), whose ratios are those with ``interp <= 16`` and ``decim <=
 256`` (2.4 MS/s to 125 kS/s is 5/96; 2.048 MS/s, 125/2048, is beyond them); the finder's 125 kHz
 restriction is inherited; and again no detection-probability figure is claimed.
+
+Raw SDR samples.  No radio delivers complex64: an RTL-SDR writes unsigned 8-bit pairs (cu8), a
+HackRF signed 8-bit pairs (cs8), USRP, Pluto, LimeSDR and most ``.sigmf-data`` files signed 16-bit
+pairs (cs16).  Torch has no complex integers, so a raw capture is an integer tensor with a
+trailing dimension of 2 - ``[L, 2]`` for a stream, ``[R, L, 2]`` for rows, dtype ``int16``,
+``int8`` or ``uint8`` - and the format follows from the dtype.  A stored component ``v`` stands for
+``x = (float(v) - bias) * scale`` in fp32, one rounding per operation, with ``bias = 127.5`` for
+``uint8`` and none for the signed dtypes; ``raw_scale(dtype)`` is the default ``scale`` (1/32768,
+1/128, 1/127.5, rounded to fp32).  ``Channelizer.run``, ``receive_wideband`` and
+``LoRaDemod.work_wideband`` take such a tensor as it is: the bank's kernel converts while it
+loads (lora_channelize_raw_batch, lora_resample_channelize_raw_batch), so the integer bytes are
+the only read of the capture and no complex64 copy of it ever exists.  ``raw_to_complex`` is the
+same conversion in torch operations, for a narrowband user to put in front of ``receive``; the two
+agree bit for bit.  ``lora_phy_amd.iq_io`` reads, writes and makes raw captures (``read_raw``,
+``iter_stream_raw``, ``write_raw``, ``quantize``).  Nothing here corrects what an SDR front end
+does to the samples - DC offset, IQ imbalance, gain steps: the conversion is the whole of it.
 """
 from __future__ import annotations
 
@@ -55,7 +71,7 @@ from . import _capi
 from .demod import DemodPlan, DemodResult, DetectMetrics, _check_iq, _require_cuda, _stream_handle
 
 __all__ = ["find_frames", "extract_frames", "receive", "lowpass_taps", "nco_table", "Channelizer",
-           "receive_wideband"]
+           "receive_wideband", "raw_scale", "raw_to_complex"]
 
 _NONE = -(1 << 62)  # "no candidate here" in the packed starts
 
@@ -235,6 +251,68 @@ def nco_table(period: int) -> np.ndarray:
     return w
 
 
+# raw sample dtypes: (LORA_IQ_* format, default scale before its rounding to fp32, bias)
+_RAW = {torch.int16: (_capi.LORA_IQ_CS16, 1.0 / 32768.0, 0.0),
+        torch.int8: (_capi.LORA_IQ_CS8, 1.0 / 128.0, 0.0),
+        torch.uint8: (_capi.LORA_IQ_CU8, 1.0 / 127.5, 127.5)}
+
+
+def _is_raw(iq) -> bool:
+    """An integer tensor: to be taken as raw samples (and refused if it is not a valid one)."""
+    return isinstance(iq, torch.Tensor) and not (iq.dtype.is_complex or iq.dtype.is_floating_point)
+
+
+def _raw_format(dtype):
+    if dtype not in _RAW:
+        raise TypeError(f"raw samples are int16 (cs16), int8 (cs8) or uint8 (cu8) tensors, not {dtype}")
+    return _RAW[dtype]
+
+
+def raw_scale(dtype) -> float:
+    """The default ``scale`` of a raw sample dtype, rounded to fp32: 1/32768 for ``torch.int16``,
+    1/128 for ``torch.int8``, 1/127.5 for ``torch.uint8``."""
+    return float(np.float32(_raw_format(dtype)[1]))
+
+
+def _scale_of(dtype, scale) -> float:
+    return raw_scale(dtype) if scale is None else float(np.float32(scale))
+
+
+def raw_to_complex(raw: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
+    """Raw samples ``[.., 2]`` (``int16``, ``int8`` or ``uint8``; I, Q) as complex64 ``[..]`` on the
+    tensor's device, by this module's definition in torch operations: ``(float(v) - bias) *
+    scale``, each operation rounded once to fp32, ``bias`` 127.5 for ``uint8`` and none otherwise;
+    ``scale`` (default ``raw_scale(raw.dtype)``) is rounded to fp32 and not checked.  Bit for bit
+    what the banks' kernels make of the same tensor."""
+    if not isinstance(raw, torch.Tensor) or raw.dim() < 1 or raw.shape[-1] != 2:
+        raise ValueError("raw samples are a [.., 2] integer tensor (I, Q)")
+    _, _, bias = _raw_format(raw.dtype)
+    x = raw.to(torch.float32)
+    if bias:
+        x = x - bias
+    x = x * _scale_of(raw.dtype, scale)
+    return torch.view_as_complex(x.contiguous())
+
+
+def _check_raw(raw: torch.Tensor, device: torch.device):
+    """``(rows, row_len, row_stride in samples, format)`` of a raw [L, 2] or [R, L, 2] tensor after
+    everything the C library cannot check about a pointer."""
+    _require_cuda(raw, "iq")
+    if raw.device != device:
+        raise ValueError(f"iq is on {raw.device}, the channelizer is on {device}")
+    fmt = _raw_format(raw.dtype)[0]
+    if raw.dim() not in (2, 3) or raw.shape[-1] != 2:
+        raise ValueError("raw samples are a [L, 2] or [R, L, 2] integer tensor (I, Q)")
+    if raw.dim() == 2:
+        raw = raw.unsqueeze(0)
+    R, L, _ = raw.shape
+    if raw.stride(2) != 1 or (L > 1 and raw.stride(1) != 2):
+        raise ValueError("raw samples must have unit stride over (I, Q) and stride 2 over the samples")
+    if R > 1 and (raw.stride(0) % 2 or raw.stride(0) < 2 * L):
+        raise ValueError("raw rows must be an even number of elements apart and must not overlap")
+    return R, L, (raw.stride(0) // 2 if R > 1 else L), fmt
+
+
 class Channelizer:
     """A digital down-converter bank on the GPU: one wideband stream in, ``C = len(steps)``
     channel streams out, each mixed down from ``steps[c] / period`` cycles per input sample above
@@ -254,7 +332,10 @@ class Channelizer:
     beyond those (2.048 MS/s to 125 kS/s is 125/2048) are not covered.
 
     The taps and the oscillator table (``nco_table(period)``) are kept on the device.
-    ``delay`` is the filter's group delay, ``(ntaps - 1) / (2 * interp)`` input samples."""
+    ``delay`` is the filter's group delay, ``(ntaps - 1) / (2 * interp)`` input samples.
+
+    ``run`` also takes raw integer samples (this module's docstring): the same kernel converts
+    them as it loads them, by ``raw_to_complex``'s arithmetic, and everything else is unchanged."""
 
     def __init__(self, decim: int, taps, period: int, steps, device=None, interp: int = 1):
         self.decim, self.period, self.interp = int(decim), int(period), int(interp)
@@ -306,10 +387,15 @@ class Channelizer:
             return _capi.check(self._lib.lora_channelize_outputs(int(L), self.ntaps, self.decim))
         return _capi.check(self._lib.lora_resample_outputs(int(L), self.ntaps, self.interp, self.decim))
 
-    def run(self, iq: torch.Tensor, first_sample: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def run(self, iq: torch.Tensor, first_sample: int = 0, out: Optional[torch.Tensor] = None,
+            scale: Optional[float] = None) -> torch.Tensor:
         """Channelize a [L] complex64 CUDA stream into [C, W], or [R, L] rows (a strided view with
         non-overlapping rows is accepted, as for ``DemodPlan.scan``) into [R, C, W]; ``W =
-        outputs(L)``.  ``first_sample`` (>= 0) is the index of ``iq[.., 0]`` in the recording, which
+        outputs(L)``.  Or raw samples: an ``int16``, ``int8`` or ``uint8`` CUDA tensor [L, 2], or
+        [R, L, 2] rows (unit stride over I, Q, stride 2 over the samples, rows any even number of
+        elements apart that does not make them overlap; any slice ``raw[k:]`` will do, the kernel
+        needs no alignment beyond one sample), converted in the kernel with ``scale`` (default
+        ``raw_scale(iq.dtype)``; ``scale`` with a complex64 input is a ``ValueError``).  ``first_sample`` (>= 0) is the index of ``iq[.., 0]`` in the recording, which
         keeps the oscillators' phase continuous across chunks: a chunk that starts at a multiple of
         ``decim`` and overlaps its predecessor by ``ntaps - decim`` samples continues its outputs
         (with ``interp > 1``: a chunk that starts at a sample ``n0`` with ``n0 * interp`` a multiple
@@ -319,9 +405,18 @@ class Channelizer:
         columns from W on are left alone and the [.., :W] view is returned.  One kernel on the
         current stream, nothing allocated besides the output, so the call can be captured in a
         HIP graph."""
-        one = isinstance(iq, torch.Tensor) and iq.dim() == 1
-        iq = _check_iq(iq, self.device)
-        R, L = iq.shape
+        raw = _is_raw(iq)
+        if raw:
+            one = iq.dim() == 2
+            R, L, row_stride, fmt = _check_raw(iq, self.device)
+            scale = _scale_of(iq.dtype, scale)
+        else:
+            if scale is not None:
+                raise ValueError("scale belongs to raw integer samples; a complex64 input has none")
+            one = isinstance(iq, torch.Tensor) and iq.dim() == 1
+            iq = _check_iq(iq, self.device)
+            R, L = iq.shape
+            row_stride = iq.stride(0) if R > 1 else L
         first_sample = int(first_sample)
         if first_sample < 0:
             raise ValueError("first_sample must be >= 0")
@@ -340,11 +435,17 @@ class Channelizer:
                                  f"{self.device}")
         if R == 0 or W == 0:
             return out[..., :W]  # nothing to launch (and an empty tensor has no address to pass)
-        # the rational entry is the integer one with interp in front of decim
-        entry, rates = ((self._lib.lora_channelize_batch, (self.decim,)) if self.interp == 1 else
-                        (self._lib.lora_resample_channelize_batch, (self.interp, self.decim)))
+        # the rational entry is the integer one with interp in front of decim; a raw entry is its
+        # float counterpart with the format and the scale behind iq
+        lib = self._lib
+        if self.interp == 1:
+            entry, rates = (lib.lora_channelize_raw_batch if raw else lib.lora_channelize_batch), (self.decim,)
+        else:
+            entry = lib.lora_resample_channelize_raw_batch if raw else lib.lora_resample_channelize_batch
+            rates = (self.interp, self.decim)
+        src = (iq.data_ptr(), fmt, scale) if raw else (iq.data_ptr(),)
         got = _capi.check(entry(
-            iq.data_ptr(), R, L, iq.stride(0) if R > 1 else L, first_sample, self.taps.data_ptr(), self.ntaps,
+            *src, R, L, row_stride, first_sample, self.taps.data_ptr(), self.ntaps,
             *rates, self.nco.data_ptr(), self.period, self._steps, C, out.data_ptr(), out.shape[-1],
             self.device.index, _stream_handle(self.device)))
         assert got == W, (got, W)
@@ -352,9 +453,10 @@ class Channelizer:
 
 
 def receive_wideband(plan: DemodPlan, chan: Channelizer, iq: torch.Tensor, frame_symbols: int,
-                     hop: Optional[int] = None, sync: int = 0x12,
-                     thresh_db: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, DemodResult]:
-    """``receive`` for a wideband capture: channelize the [L] complex64 CUDA stream ``iq`` with
+                     hop: Optional[int] = None, sync: int = 0x12, thresh_db: float = 0.0,
+                     scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, DemodResult]:
+    """``receive`` for a wideband capture: channelize the [L] complex64 CUDA stream ``iq`` (or the
+    raw [L, 2] integer stream, converted with ``scale`` as ``Channelizer.run`` does) with
     ``chan``, scan all channel rows at once, find the frames of ``frame_symbols`` data symbols in
     each row by the finder's rule, gather them and demodulate them.
 
@@ -371,13 +473,13 @@ def receive_wideband(plan: DemodPlan, chan: Channelizer, iq: torch.Tensor, frame
     no frame found the tensors are empty and no demod call is made."""
     if not plan.dechirp:
         raise ValueError("receive_wideband needs a plan with dechirp=True: the finder reads dechirped peaks")
-    if not isinstance(iq, torch.Tensor) or iq.dim() != 1:
-        raise ValueError("receive_wideband takes one [L] stream")
+    if not isinstance(iq, torch.Tensor) or iq.dim() != (2 if _is_raw(iq) else 1):
+        raise ValueError("receive_wideband takes one [L] stream (raw samples: [L, 2])")
     if chan.device != plan.device:
         raise ValueError(f"the channelizer is on {chan.device}, the plan is on {plan.device}")
     hop = plan.step // 4 if hop is None else int(hop)
     N, step, k, sw0, sw1, frame_len = _geometry(hop, plan.sf, plan.osr, frame_symbols, sync, plan.bw)
-    rows = chan.run(iq)  # [C, Wc]
+    rows = chan.run(iq, scale=scale)  # [C, Wc]
     C, Wc = rows.shape
     dev = plan.device
     found = []
