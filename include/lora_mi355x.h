@@ -372,6 +372,80 @@ int64_t lora_resample_channelize_raw_batch(const void* iq, int format, float sca
                                            int64_t period, const int32_t* steps, int64_t channels, float* out,
                                            int64_t out_stride, int device, void* stream);
 
+/* Synthesis bank: the inverse of the down-converter banks.  `channels` streams at the modulator's
+ * rate in, one wideband stream out, from one kernel that writes each wideband sample once.  The
+ * reference has no synthesiser; this definition, like the banks', is the library's own.
+ *   in     `rows` x `channels` streams of `chan_len` complex samples: stream (r, c) is at
+ *          in + 2*(r*channels + c)*in_stride floats (device);
+ *   taps   `ntaps` real fp32 values h[j] of a prototype low-pass filter at the OUTPUT rate
+ *          (device); a gain of `interp` makes up for the zero-stuffing;
+ *   interp the integer up-sampling factor U;
+ *   nco    `period` complex fp32 values w[m] = (wr[m], wi[m]) (device): an input, as for the
+ *          banks; to put channel c at k_c / period cycles per output sample above the centre it
+ *          is exp(+2 pi i m / period) rounded to fp32, the conjugate of the banks' table;
+ *   steps  a HOST array of `channels` ints k_c, any int, each reduced mod `period` (to
+ *          0 .. period-1) on the host; they travel in the kernel's arguments;
+ *   gains  a HOST array of `channels` fp32 values g_c, which also travel in the kernel's
+ *          arguments, so the call can be captured in a graph;
+ *   first_sample (>= 0) the index of output 0 in the transmitted recording: it keeps the
+ *          oscillators' phase continuous across chunks;
+ *   out    `rows` rows: output t of row r is sample r*out_stride + t of out (device).
+ * All arithmetic is fp32, one rounding per operation, no contraction, and every accumulator
+ * starts at +0.0f.  With P = ceil(ntaps / U):
+ *   1. the gain, once per input sample:   ar = g_c*xr        ai = g_c*xi
+ *   2. polyphase interpolation, "valid" outputs only.  For output t: p = t mod U, q = t / U,
+ *      K = p >= ntaps ? 0 : ceil((ntaps - p) / U), and for i = 0 .. K-1 in this order
+ *        sr = sr + h[p + i*U]*ar[q + P-1 - i]    si = si + h[p + i*U]*ai[q + P-1 - i]
+ *      (the zero-stuffed terms are never formed; K == 0 gives (+0.0f, +0.0f));
+ *   3. the mix, m = (k_c * (first_sample + t)) mod period (in integers, non-negative):
+ *        zr = sr*wr[m] - si*wi[m]        zi = sr*wi[m] + si*wr[m]
+ *   4. the sum over the channels, c = 0 .. channels-1 in this order from +0.0f:
+ *        yr = yr + zr        yi = yi + zi.
+ * Infinities and NaN propagate as this arithmetic makes them, with lora_channelize_batch's
+ * caveat about a NaN's sign and payload.
+ * A row gives W = chan_len < P ? 0 : (chan_len - P + 1)*U outputs and no output reads outside
+ * its streams.  Chunks: a chunk continues its predecessor's outputs when it overlaps it by P-1
+ * channel samples and is given first_sample advanced by the predecessor's W.  Delay: channel
+ * sample m is centred on output m*U + (ntaps-1)/2 - (P-1)*U.
+ * Only an integer up-sampling factor is covered; a rational up-rate (interp / decim) is not.
+ *
+ * lora_synthesize_raw_batch is lora_synthesize_batch with `void* out, int format, float
+ * inv_scale` in place of `float* out`: the row is stored as cs16, cs8 or cu8 samples (LORA_IQ_*
+ * above; out_stride stays in samples).  Per component, from the y of step 4:
+ *   v = y*inv_scale (one product);   for cu8 only v = v + 127.5f (one sum);
+ *   code = clamp(rintf(v), lo, hi), ties to even, [lo, hi] the format's code range;
+ *   a NaN v stores the format's zero: 0 for the signed formats, 128 for cu8.
+ * inv_scale is the caller's fp32 value and is not checked; the usual values are 32768, 128 and
+ * 127.5, all exact.  The bits stored equal this rule applied to lora_synthesize_batch's output.
+ * (They equal a division by scale = 1 / inv_scale followed by the same rounding only where the
+ * division and the product round alike: power-of-two scales, the cs16 and cs8 defaults.)
+ * out need only be aligned to one sample (8 bytes of complex64, 4 of cs16, 2 of cs8 and cu8), so
+ * any sample of a larger transmit buffer can be a row's first; the kernel stores 16 bytes at a
+ * time where the address allows and single samples at a row's ragged ends, and the bits are
+ * the same at every alignment.
+ *
+ * lora_synthesize_outputs: host arithmetic only; W, or LORA_EINVAL for a negative chan_len,
+ * ntaps < 1, interp < 1 or a chan_len * interp beyond 64 bits.
+ * lora_synthesize_batch, lora_synthesize_raw_batch: enqueue one kernel on `stream` of `device`,
+ * allocate and synchronise nothing, need no workspace, and fully write columns 0 .. W-1 of every
+ * row and nothing beyond them.  rows == 0 or W == 0: no launch (and NULL pointers allowed).
+ * LORA_EINVAL, before any HIP call: negative sizes or first_sample, interp outside 1..64, ntaps
+ * outside 1..512, period outside 1..4096, channels outside 1..32, chan_len * interp >= 2^31,
+ * in_stride < chan_len with more than one stream, out_stride < W with more than one row, an out
+ * that is not aligned to one sample, a `format` that is none of the three (0 included), a grid
+ * beyond 2^31 (rows * ceil(W / 1024)), and with work to do a NULL in, taps, nco, steps, gains
+ * or out.  Returns W. */
+int64_t lora_synthesize_outputs(int64_t chan_len, int64_t ntaps, int64_t interp);
+int64_t lora_synthesize_batch(const float* in, int64_t rows, int64_t chan_len, int64_t in_stride,
+                              int64_t first_sample, const float* taps, int64_t ntaps, int64_t interp,
+                              const float* nco, int64_t period, const int32_t* steps, const float* gains,
+                              int64_t channels, float* out, int64_t out_stride, int device, void* stream);
+int64_t lora_synthesize_raw_batch(const float* in, int64_t rows, int64_t chan_len, int64_t in_stride,
+                                  int64_t first_sample, const float* taps, int64_t ntaps, int64_t interp,
+                                  const float* nco, int64_t period, const int32_t* steps, const float* gains,
+                                  int64_t channels, void* out, int format, float inv_scale, int64_t out_stride,
+                                  int device, void* stream);
+
 /* lora_modulate for `frames` independent frames: symbols [frames][sym_count] ->
  * iq [frames][(sym_count+2)*N*osr] (2 sync up-chirps then one chirp per symbol,
  * phase-continuous within a frame, LoRaMod.cpp:8-41).  Returns samples per frame. */

@@ -1,6 +1,7 @@
 // lora_iq_format.h — the sample formats the down-converter banks read (include/lora_mi355x.h,
 // LORA_IQ_*; 0 is complex64 here) and the one loop of either bank that knows them: the load in
-// front of `mix` (csrc/lora_channelize.hip, csrc/lora_resample.hip).
+// front of `mix` (csrc/lora_channelize.hip, csrc/lora_resample.hip); and the store side of the
+// same formats, fp32 to a stored code, for the synthesis bank (csrc/lora_synth.hip).
 //
 // A stored integer component v becomes x = ((float)v - bias) * scale, fp32, one rounding per
 // operation, no contraction; bias is 127.5f for cu8 and nothing for the signed formats.
@@ -101,6 +102,30 @@ __device__ __forceinline__ void load_samples(const void* iq, int64_t first, int 
       if (s0 + 1 >= 0 && s0 + 1 < cnt) single(s0 + 1);
     }
   }
+}
+
+// The store side (csrc/lora_synth.hip): an fp32 component y to the stored code of an integer
+// format, v = y * inv_scale (one product), for cu8 v = v + 127.5f (one sum), then
+// clamp(rintf(v), lo, hi) with ties to even; a NaN v stores the format's zero (0, or 128 for cu8)
+template <int F>
+__device__ __forceinline__ int iq_store_code(float y, float inv_scale) {
+  static_assert(F == LORA_IQ_CS16 || F == LORA_IQ_CS8 || F == LORA_IQ_CU8, "unknown sample format");
+  constexpr float lo = F == LORA_IQ_CS16 ? -32768.0f : F == LORA_IQ_CS8 ? -128.0f : 0.0f;
+  constexpr float hi = F == LORA_IQ_CS16 ? 32767.0f : F == LORA_IQ_CS8 ? 127.0f : 255.0f;
+  float v = y * inv_scale;
+  if constexpr (F == LORA_IQ_CU8) v = v + 127.5f;
+  if (v != v) return F == LORA_IQ_CU8 ? 128 : 0;
+  return (int)fminf(fmaxf(rintf(v), lo), hi);
+}
+
+// The codes of I and Q as one stored sample, I in the low half (little-endian): 32 bits of cs16,
+// 16 of an 8-bit format
+template <int F>
+__device__ __forceinline__ unsigned iq_pack(int ci, int cq) {
+  if constexpr (F == LORA_IQ_CS16)
+    return ((unsigned)ci & 0xffffu) | ((unsigned)cq << 16);
+  else
+    return ((unsigned)ci & 0xffu) | (((unsigned)cq & 0xffu) << 8);
 }
 
 // The raw entries' checks that the float entries do not have (host): the format is one of

@@ -6,7 +6,8 @@ current torch stream.  Host-side coding helpers (Hamming, Gray, interleave,
 whitening, CRC) are in :mod:`lora_phy_amd.codes`, their batched device counterparts
 (symbols <-> payload bytes, one kernel per call) in :mod:`lora_phy_amd.codec`; the
 phy.hpp-style functional API is in :mod:`lora_phy_amd.phy`; receiving a continuous stream
-(sliding detector scan, frame finder) is in :mod:`lora_phy_amd.stream`.
+(sliding detector scan, frame finder), wideband receive (the channelizer banks) and wideband
+transmit (the synthesis bank) are in :mod:`lora_phy_amd.stream`.
 """
 from . import _capi, codec, codes, iq_io, phy, shard, stream  # noqa: F401
 from ._capi import LoraError

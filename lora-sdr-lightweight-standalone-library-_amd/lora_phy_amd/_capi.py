@@ -49,6 +49,9 @@ EXPORTED_SYMBOLS = (
     "lora_resample_channelize_batch",
     "lora_channelize_raw_batch",
     "lora_resample_channelize_raw_batch",
+    "lora_synthesize_outputs",
+    "lora_synthesize_batch",
+    "lora_synthesize_raw_batch",
     "lora_mod_batch",
     "lora_estimate_offsets_batch",
     "lora_compensate_offsets_batch",
@@ -171,6 +174,18 @@ def lib() -> C.CDLL:
     L.lora_resample_channelize_raw_batch.restype = C.c_int64
     L.lora_resample_channelize_raw_batch.argtypes = ([C.c_void_p, C.c_int, C.c_float] +
                                                      L.lora_resample_channelize_batch.argtypes[1:])
+    # the synthesis bank (csrc/lora_synth.hip): steps and gains are host arrays; the raw entry has
+    # (out, format, inv_scale) in place of out
+    L.lora_synthesize_outputs.restype = C.c_int64
+    L.lora_synthesize_outputs.argtypes = [C.c_int64, C.c_int64, C.c_int64]
+    L.lora_synthesize_batch.restype = C.c_int64
+    L.lora_synthesize_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_float), C.c_int64, C.c_void_p, C.c_int64, C.c_int,
+                                        C.c_void_p]
+    L.lora_synthesize_raw_batch.restype = C.c_int64
+    L.lora_synthesize_raw_batch.argtypes = (L.lora_synthesize_batch.argtypes[:14] + [C.c_int, C.c_float] +
+                                            L.lora_synthesize_batch.argtypes[14:])
     L.lora_mod_batch.restype = C.c_int64
     L.lora_mod_batch.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_float, C.c_uint8, C.c_void_p,
                                  C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]

@@ -63,6 +63,22 @@ class LoRaMod:
             iq = torch.cat([iq, pad], dim=-1)
         return iq
 
+    def work_wideband(self, synth, symbols, channel, starts, chan_len: int, dtype=None) -> torch.Tensor:
+        """``work`` into a wideband stream (``lora_phy_amd.stream.transmit_wideband`` with this
+        block's frames): modulate the [K, S] ``symbols``, put frame i at sample ``starts[i]`` (in
+        channel samples) of channel ``channel[i]`` of ``synth``, a ``stream.Synthesizer``, among
+        ``chan_len`` samples per channel, and synthesize the one wideband stream: [W] complex64,
+        or with ``dtype`` ``torch.int16`` / ``int8`` / ``uint8`` the raw [W, 2] samples that
+        ``iq_io.write_raw`` writes for a radio.  This block's rate (bw * ovs) is the channel rate:
+        the wideband rate is ``synth.interp`` times it.  The padding of ``work`` is part of each
+        frame."""
+        from . import stream
+
+        frames = self.work(symbols)
+        if frames.dim() == 1:
+            frames = frames.unsqueeze(0)
+        return stream.transmit_wideband(synth, frames, channel, starts, chan_len, dtype=dtype)
+
     def work_payload(self, payload, chain: str = "library", append_crc: bool = False) -> torch.Tensor:
         """Encode payload bytes ([F, n] or [n] uint8) on the device (lora_phy_amd.codec), then
         modulate.  ``chain="library"``: lora_encode (LoRaEncoder.cpp:8-19), with

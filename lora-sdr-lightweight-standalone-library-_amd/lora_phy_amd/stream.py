@@ -59,6 +59,15 @@ same conversion in torch operations, for a narrowband user to put in front of ``
 agree bit for bit.  ``lora_phy_amd.iq_io`` reads, writes and makes raw captures (``read_raw``,
 ``iter_stream_raw``, ``write_raw``, ``quantize``).  Nothing here corrects what an SDR front end
 does to the samples - DC offset, IQ imbalance, gain steps: the conversion is the whole of it.
+
+Wideband transmit.  ``Synthesizer`` is the inverse of ``Channelizer``: one kernel scales every
+channel stream by its gain, interpolates it by an integer ``interp``, mixes it up to its centre
+and sums the channels into the one wideband stream a radio transmits, as complex64 or as the raw
+integer samples the radio takes (lora_synthesize_batch, lora_synthesize_raw_batch; the exact
+arithmetic is in include/lora_mi355x.h and is this project's own: the reference has no
+synthesiser).  ``transmit_wideband`` places modulated frames in their channels and runs it, and
+``LoRaMod.work_wideband`` modulates first.  Rational up-rates are not covered, and no
+spectral-mask or adjacent-channel figure is claimed.
 """
 from __future__ import annotations
 
@@ -71,7 +80,7 @@ from . import _capi
 from .demod import DemodPlan, DemodResult, DetectMetrics, _check_iq, _require_cuda, _stream_handle
 
 __all__ = ["find_frames", "extract_frames", "receive", "lowpass_taps", "nco_table", "Channelizer",
-           "receive_wideband", "raw_scale", "raw_to_complex"]
+           "receive_wideband", "raw_scale", "raw_to_complex", "Synthesizer", "transmit_wideband"]
 
 _NONE = -(1 << 62)  # "no candidate here" in the packed starts
 
@@ -500,3 +509,197 @@ def receive_wideband(plan: DemodPlan, chan: Channelizer, iq: torch.Tensor, frame
     frames = _gather(rows.reshape(-1), channel_t * Wc + starts_t, frame_len)
     return channel_t, starts_t, plan.run(frames)
 
+
+
+# raw output dtypes of the synthesis bank: the default inv_scale (exact in fp32)
+_INV_SCALE = {torch.int16: 32768.0, torch.int8: 128.0, torch.uint8: 127.5}
+
+
+class Synthesizer:
+    """A synthesis bank on the GPU, the inverse of ``Channelizer``: ``C = len(steps)`` channel
+    streams in, one wideband stream at ``interp`` times their rate out.  Channel c is multiplied
+    by ``gains[c]`` (default 1), interpolated by ``interp`` with the real ``taps`` - a prototype
+    low-pass at the OUTPUT rate, ``lowpass_taps(ntaps, 0.5 / interp, gain=interp)`` - mixed up to
+    ``steps[c] / period`` cycles per output sample above the centre, and the channels are summed.
+    One kernel (lora_synthesize_batch) writes every wideband sample once, as complex64 or, with
+    ``dtype``, as the raw integer samples a radio takes (lora_synthesize_raw_batch: ``int16`` for a
+    USRP or Pluto, ``int8`` for a HackRF, ``uint8``).  The arithmetic is defined exactly in
+    include/lora_mi355x.h (the definition is this library's own: the reference has no
+    synthesiser), so a host restatement reproduces every bit.
+
+    Limits: ``interp`` 1..64, 1..512 taps, ``period`` 1..4096, 1..32 channels; channel centres
+    are multiples of ``fs / period``.  Only an integer ``interp`` is covered: a rational up-rate
+    (interp / decim) is not.  Nothing is claimed about the spectrum beyond what the taps do: no
+    spectral-mask or adjacent-channel figure, and nothing of a DAC or a front end.
+
+    The taps and the oscillator table - ``exp(+2 pi i m / period)``, the conjugate of
+    ``nco_table(period)`` - are kept on the device.  ``delay``: channel sample m is centred on
+    output ``m * interp + delay``, ``delay = (ntaps - 1) / 2 - (P - 1) * interp`` with ``P =
+    ceil(ntaps / interp)`` (it is negative when the first "valid" output lies past the centre of
+    channel sample 0)."""
+
+    def __init__(self, interp: int, taps, period: int, steps, gains=None, device=None):
+        self.interp, self.period = int(interp), int(period)
+        h = np.ascontiguousarray(taps, np.float32)
+        self.steps = [int(k) for k in steps]
+        if not 1 <= self.interp <= 64:
+            raise ValueError("interp must be in 1..64")
+        if h.ndim != 1 or not 1 <= h.shape[0] <= 512:
+            raise ValueError("taps must be 1..512 real values")
+        if not 1 <= self.period <= 4096:
+            raise ValueError("period must be in 1..4096")
+        if not 1 <= len(self.steps) <= 32 or any(abs(k) >= 1 << 31 for k in self.steps):
+            raise ValueError("steps must be 1..32 ints")
+        self.ntaps, self.channels = int(h.shape[0]), len(self.steps)
+        g = np.ones(self.channels, np.float32) if gains is None else np.ascontiguousarray(gains, np.float32)
+        if g.shape != (self.channels,):
+            raise ValueError("gains must be one real value per channel")
+        self.gains = [float(v) for v in g]
+        self.P = -(-self.ntaps // self.interp)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise TypeError("Synthesizer runs on a CUDA (HIP) device; there is no CPU fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._lib = _capi.lib()
+        self._steps = (_capi.C.c_int32 * self.channels)(*self.steps)
+        self._gains = (_capi.C.c_float * self.channels)(*self.gains)
+        self.taps = torch.from_numpy(h.copy()).to(self.device)
+        self.nco = torch.from_numpy(np.conj(nco_table(self.period))).to(self.device)
+
+    @property
+    def delay(self) -> float:
+        return (self.ntaps - 1) / 2 - (self.P - 1) * self.interp
+
+    def _outputs(self, chan_len: int) -> int:
+        return 0 if chan_len < self.P else (chan_len - self.P + 1) * self.interp
+
+    def outputs(self, chan_len: int) -> int:
+        """Wideband samples for channel streams of ``chan_len`` samples: ``0 if chan_len < P else
+        (chan_len - P + 1) * interp`` (lora_synthesize_outputs)."""
+        return _capi.check(self._lib.lora_synthesize_outputs(int(chan_len), self.ntaps, self.interp))
+
+    def run(self, chans: torch.Tensor, first_sample: int = 0, out: Optional[torch.Tensor] = None, dtype=None,
+            inv_scale: Optional[float] = None) -> torch.Tensor:
+        """Synthesize [C, Lc] complex64 CUDA channel streams into a [W] complex64 wideband stream,
+        or [R, C, Lc] into [R, W]; ``W = outputs(Lc)``.  The streams have unit sample stride and
+        are any equal number of samples >= Lc apart (rows ``C`` times that), so a [.., :Lc] view
+        of a larger tensor is accepted.  With ``dtype`` ``torch.int16``, ``torch.int8`` or
+        ``torch.uint8`` the result is raw samples [W, 2] or [R, W, 2] (I, Q), each component
+        ``clamp(rint(y * inv_scale (+ 127.5 for uint8)))`` in fp32 with ties to even and NaN stored
+        as the format's zero; ``inv_scale`` defaults to 32768, 128 or 127.5 and is rounded to fp32
+        (``inv_scale`` without ``dtype`` is a ``ValueError``).  That is ``iq_io.quantize`` of the
+        complex64 result wherever its division by ``scale`` and this product round alike - the
+        power-of-two scales, i.e. the ``int16`` and ``int8`` defaults - in one kernel and with no
+        complex64 copy.  ``first_sample`` (>= 0) is the index of output 0 in the transmitted
+        recording, which keeps the oscillators' phase continuous across chunks: a chunk whose
+        streams overlap its predecessor's by ``P - 1`` samples and whose ``first_sample`` is
+        advanced by the predecessor's ``W`` continues its outputs.
+        ``out``: a tensor of the result's dtype to write into, [>= W] (or [R, >= W]; raw: with a
+        trailing 2), unit stride within a row and rows that do not overlap; any slice ``buf[k:]``
+        of a transmit buffer will do, the kernel needs no alignment beyond one sample.  Its
+        columns from W on are left alone and the [.., :W] view is returned.  One kernel on the
+        current stream, nothing allocated besides the output, so the call can be captured in a
+        HIP graph."""
+        if dtype is None:
+            if inv_scale is not None:
+                raise ValueError("inv_scale belongs to a raw integer dtype; a complex64 output has none")
+            odt = torch.complex64
+        else:
+            if dtype not in _INV_SCALE:
+                raise TypeError(f"raw samples are int16 (cs16), int8 (cs8) or uint8 (cu8), not {dtype}")
+            odt = dtype
+            inv_scale = float(np.float32(_INV_SCALE[dtype] if inv_scale is None else inv_scale))
+        raw = dtype is not None
+        _require_cuda(chans, "chans")
+        if chans.device != self.device:
+            raise ValueError(f"chans is on {chans.device}, the synthesizer is on {self.device}")
+        if chans.dtype != torch.complex64:
+            raise TypeError("chans must be complex64")
+        if chans.dim() not in (2, 3) or chans.shape[-2] != self.channels:
+            raise ValueError(f"chans must be [{self.channels}, Lc] or [R, {self.channels}, Lc]")
+        one = chans.dim() == 2
+        if one:
+            chans = chans.unsqueeze(0)
+        R, C, Lc = chans.shape
+        in_stride = chans.stride(1) if C > 1 else (chans.stride(0) // C if R > 1 else Lc)
+        if ((Lc > 1 and chans.stride(2) != 1) or (R * C > 1 and in_stride < Lc)
+                or (R > 1 and chans.stride(0) != C * in_stride)):
+            raise ValueError("chans must have unit sample stride, streams an equal number of samples >= Lc apart "
+                             "and rows C times that")
+        first_sample = int(first_sample)
+        if first_sample < 0:
+            raise ValueError("first_sample must be >= 0")
+        W = self._outputs(Lc)
+        tail = (2,) if raw else ()
+        if out is None:
+            out = torch.empty(((W,) if one else (R, W)) + tail, dtype=odt, device=self.device)
+        else:
+            _require_cuda(out, "out")
+            if out.dtype != odt:
+                raise TypeError(f"out must be {odt}")
+            lead = () if one else (R,)
+            nd = len(lead) + 1 + len(tail)
+            ok = (out.device == self.device and out.dim() == nd and tuple(out.shape[:len(lead)]) == lead
+                  and out.shape[len(lead)] >= W and (not raw or (out.shape[-1] == 2 and out.stride(-1) == 1)))
+            per = 2 if raw else 1  # elements per sample
+            if ok and out.shape[len(lead)] > 1:
+                ok = out.stride(len(lead)) == per
+            if ok and R > 1 and not one:
+                ok = out.stride(0) % per == 0 and out.stride(0) >= per * W
+            if not ok:
+                raise ValueError(f"out must be a {odt} {list(lead) + ['>=%d' % W] + list(tail)} tensor on "
+                                 f"{self.device} with unit stride within a row and rows that do not overlap")
+        view = out[:W] if one else out[:, :W]
+        if R == 0 or W == 0:
+            return view  # nothing to launch (and an empty tensor has no address to pass)
+        out_stride = (out.stride(0) // (2 if raw else 1)) if (not one and R > 1) else out.shape[0 if one else 1]
+        head = (chans.data_ptr(), R, Lc, in_stride, first_sample, self.taps.data_ptr(), self.ntaps, self.interp,
+                self.nco.data_ptr(), self.period, self._steps, self._gains, C, out.data_ptr())
+        tail_args = (out_stride, self.device.index, _stream_handle(self.device))
+        if raw:
+            got = self._lib.lora_synthesize_raw_batch(*head, _RAW[dtype][0], inv_scale, *tail_args)
+        else:
+            got = self._lib.lora_synthesize_batch(*head, *tail_args)
+        got = _capi.check(got)
+        assert got == W, (got, W)
+        return view
+
+
+def transmit_wideband(synth: Synthesizer, frames: torch.Tensor, channel, starts, chan_len: int,
+                      first_sample: int = 0, out: Optional[torch.Tensor] = None, dtype=None,
+                      inv_scale: Optional[float] = None) -> torch.Tensor:
+    """The inverse of ``receive_wideband``: put K frames into the channels of one wideband stream.
+    ``frames`` is a [K, frame_len] complex64 CUDA tensor (``LoRaMod.work``'s); frame i goes to
+    samples ``starts[i] .. starts[i] + frame_len - 1`` of channel ``channel[i]`` (host ints, in
+    CHANNEL samples) of a zeroed [C, chan_len] tensor - one torch index assignment - which
+    ``synth.run`` then turns into the wideband stream: [W] complex64, or [W, 2] raw samples with
+    ``dtype``; ``first_sample``, ``out``, ``dtype`` and ``inv_scale`` are ``Synthesizer.run``'s.
+    Channel sample m is centred on output ``m * synth.interp + synth.delay``.  A frame outside
+    its channel's ``chan_len`` samples, a channel outside 0 .. C-1 or two frames that overlap in
+    one channel are a ``ValueError``."""
+    _require_cuda(frames, "frames")
+    if frames.dtype != torch.complex64 or frames.dim() != 2:
+        raise ValueError("frames must be a [K, frame_len] complex64 tensor")
+    if frames.device != synth.device:
+        raise ValueError(f"frames is on {frames.device}, the synthesizer is on {synth.device}")
+    K, frame_len = frames.shape
+    chan_len = int(chan_len)
+    ch = np.asarray(channel.cpu() if isinstance(channel, torch.Tensor) else channel, np.int64).reshape(-1)
+    st = np.asarray(starts.cpu() if isinstance(starts, torch.Tensor) else starts, np.int64).reshape(-1)
+    if len(ch) != K or len(st) != K:
+        raise ValueError("channel and starts must have one entry per frame")
+    if K and (ch.min() < 0 or ch.max() >= synth.channels):
+        raise ValueError(f"channel must be in 0..{synth.channels - 1}")
+    if K and (st.min() < 0 or st.max() + frame_len > chan_len):
+        raise ValueError("every frame must lie inside its channel's chan_len samples")
+    order = np.lexsort((st, ch))
+    for i, j in zip(order[:-1], order[1:]):
+        if ch[i] == ch[j] and st[j] < st[i] + frame_len:
+            raise ValueError(f"frames {int(i)} and {int(j)} overlap in channel {int(ch[i])}")
+    chans = torch.zeros((synth.channels, chan_len), dtype=torch.complex64, device=synth.device)
+    if K and frame_len:
+        base = torch.from_numpy(ch * chan_len + st).to(synth.device)
+        idx = base[:, None] + torch.arange(frame_len, device=synth.device)
+        chans.view(-1)[idx] = frames
+    return synth.run(chans, first_sample, out, dtype, inv_scale)
