@@ -245,6 +245,57 @@ int64_t lora_detect_scan_windows(const lora_demod_plan* plan, int64_t row_len, i
 int64_t lora_detect_scan_batch(lora_demod_plan* plan, const float* iq, int64_t rows, int64_t row_len,
                                int64_t row_stride, int64_t hop, const lora_symbol_metrics* out, void* stream);
 
+/* The frame finder on the device: frame starts from the scan's outputs, by the rule that
+ * lora_phy_amd/stream.py states (the reference has no frame detector; the rule is the library's
+ * own).  The inputs are three of lora_detect_scan_batch's outputs for `rows` rows of W windows,
+ * made with this hop by a dechirping plan of this sf and osr at bw 125 kHz (the entry knows no
+ * bandwidth and cannot check it): power, power_avg and index, laid out [rows][stride] with
+ * column w.  With N = 2^sf, step = N*osr, k = step / hop, sw0 = (sync >> 4) << (sf - 4),
+ * sw1 = (sync & 15) << (sf - 4) (sync taken mod 256), frame_len = (frame_symbols + 2) * step:
+ *   snr[w] = power[w] - power_avg[w], one fp32 subtraction, and ok[w] = snr[w] >= thresh_db in
+ *     fp32: NaN fails, +inf passes;
+ *   window w, 0 <= w < W - k, is a candidate when ok[w], ok[w + k] and
+ *     (index[w + k] - index[w]) mod N == (sw1 - sw0) mod N;
+ *   d = (index[w] - sw0) mod N, minus N when d >= N/2, and start = w*hop - d*osr in int64;
+ *   the greedy pass runs in increasing w from ceil(max(first - step/2, 0) / hop): a candidate
+ *     with start >= first, start >= 0 and start + frame_len <= row_len is accepted, first becomes
+ *     start + frame_len and the pass continues at the smallest w' > w with w'*hop >= first -
+ *     step/2; anything else moves on to w + 1.
+ * `first` is a device array of one int64 per row, or NULL for 0 in every row.  Per row:
+ *   count   the frames the pass accepts; the pass does not depend on capacity, so count may
+ *           exceed it;
+ *   starts  [rows][capacity]: the first min(count, capacity) accepted starts, increasing, then
+ *           -1 in every further slot;
+ *   end     first as the pass leaves it: the end of the last accepted frame, or the first given
+ *           when none was accepted - what a chunked caller carries into its next chunk.
+ * All three equal the rule applied on the host, as integers.
+ *
+ * lora_find_frames_batch: enqueues one kernel on `stream` of params.device, allocates and
+ * synchronises nothing, needs no workspace, and fully writes count, end and all `capacity` slots
+ * of starts for every row - also for rows with W <= k (count 0, end = first) and for capacity 0.
+ * One workgroup per row; no workgroup waits on another.  rows == 0: no launch.  LORA_EINVAL,
+ * before any HIP call: a NULL params, a NULL count or end, a NULL starts with capacity > 0 or
+ * NULL metrics with W > k (each with rows > 0), sf outside 6..12, osr outside 1..65536, hop < 1,
+ * hop not dividing step or step / hop < 2, frame_symbols outside 0 .. 2^31 - 1, negative rows,
+ * W, stride, row_len or capacity, stride < W with more than one row, W >= 2^31, rows >= 2^31.
+ * Returns rows.
+ * lora_find_frames_tile: the windows per tile of the kernel's pass (its state crosses a tile
+ * boundary every so many windows); host arithmetic only. */
+typedef struct {
+  unsigned sf;
+  unsigned osr;
+  unsigned sync;
+  float thresh_db;
+  int64_t hop;
+  int64_t frame_symbols;
+  int device;
+} lora_find_params;
+int64_t lora_find_frames_tile(void);
+int64_t lora_find_frames_batch(const lora_find_params* params, const float* power, const float* power_avg,
+                               const uint16_t* index, int64_t rows, int64_t W, int64_t stride,
+                               const int64_t* first, int64_t row_len, int64_t capacity, int64_t* starts,
+                               int32_t* count, int64_t* end, void* stream);
+
 /* Digital down-converter bank: one wideband stream in, `channels` streams at the demodulator's
  * rate out, from one read of the wideband data.  The reference has no channelizer; this
  * definition is the library's own (like the finder's rule and the soft bits).

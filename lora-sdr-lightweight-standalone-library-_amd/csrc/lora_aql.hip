@@ -42,7 +42,7 @@ namespace {
 
 constexpr unsigned kSlotBytes = 1024;  // kernarg slot per packet (explicit + 256 hidden)
 constexpr int kCache = 256;  // kernel objects resolved (the drop-in's warm-up: every SF and window)
-constexpr int kMaxExec = 8;
+constexpr int kMaxExec = 16;  // code objects of this library: one per translation unit with a kernel (9)
 
 struct AqlKernel {
   const void* fn;

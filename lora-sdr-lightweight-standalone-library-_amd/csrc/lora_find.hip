@@ -1,0 +1,349 @@
+// lora_find.hip — the frame finder on the device (lora_find_frames_batch).
+//
+// The finder's rule (include/lora_mi355x.h; lora_phy_amd/stream.py states it first) has a
+// parallel half and a serial half.  Whether window w is a candidate, and the start it refines
+// to, depend on the scan's outputs at w and w + k alone; the greedy pass then walks the
+// candidates in order, carrying `first`.  Rejections are permanent - `first` and the pass's
+// position only grow, and the tests against 0 and row_len do not depend on the pass - so the
+// next frame the serial pass accepts from position p is the LOWEST w >= p that is a candidate,
+// fits the row and has start >= first.  That is a find-first-set.
+//
+// One workgroup of kThreads takes one row, in tiles of kFindTile windows, and each tile goes
+// through three stages:
+//   build  each wave takes 64 consecutive windows at a time, loads the three metrics at w and
+//          w + k (coalesced, all of the wave's loads issued before the first is used), and
+//          leaves in LDS one 64-bit ballot word - bit set: candidate with 0 <= start <= row_len -
+//          frame_len - and the 64 index values;
+//   link   what the pass accepts after a frame depends on that frame alone (its end is the new
+//          `first`, its window the new position), so for every set bit of the tile its successor
+//          - the lowest set bit from the jump on whose start is not before this one's end - is
+//          found by one lane, all bits in parallel, and left in LDS (none: the chain leaves the
+//          tile);
+//   walk   wave 0 finds the first frame of the tile from the state it carries (64 mask words,
+//          one per lane, and a ballot to skip to the next non-empty word; the 64 starts of that
+//          word, one per lane; a ballot of start >= first; the lowest set lane), then follows the
+//          successors: one dependent LDS read per accepted frame.
+// Every step of the walk either accepts a frame, and the successor is a later window of the
+// tile, or moves the position to a later word; the position is bounded by W - k.  The stages
+// are pipelined over three tile buffers: while wave 0 walks tile t, the other waves link tile
+// t + 1 and build tile t + 2, with one barrier per tile.  No workgroup waits on another, nothing
+// is read back from global memory, and there is no workspace.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/lora_mi355x.h"
+#include "lora_internal.h"
+
+namespace lora {
+namespace {
+
+constexpr int kThreads = 1024;
+constexpr int kWaves = kThreads / 64;
+constexpr int kFindTile = 4096;             // windows per tile
+constexpr int kTileWords = kFindTile / 64;  // ballot words per tile
+
+struct FindArgs {
+  const float* power;
+  const float* power_avg;
+  const uint16_t* index;
+  const int64_t* first;  // [rows] or null
+  int64_t* starts;       // [rows][capacity]
+  int32_t* count;        // [rows]
+  int64_t* end;          // [rows]
+  int64_t stride, capacity;
+  int64_t n;             // W - k: windows the pass may test (may be <= 0)
+  int64_t hop, osr, half_step, frame_len;
+  int64_t last_start;    // row_len - frame_len: the last start that fits (may be < 0)
+  int64_t lead_q;        // frame_len - step / 2 = lead_q * hop + lead_r, 0 <= lead_r < hop
+  int lead_r, hop32;
+  int k, N, sw0, dsync;  // dsync = (sw1 - sw0) mod N
+  float thresh;
+};
+
+struct Tile {
+  unsigned long long mask[kTileWords];
+  uint16_t index[kFindTile];
+};
+constexpr unsigned kNoSucc = 0xFFFFu;  // in a tile's successor array: the chain leaves the tile
+
+// d folded to [-N/2, N/2) and the refined start of window w whose peak is `idx`.
+__device__ __forceinline__ int64_t refined_start(const FindArgs& a, int64_t w, int idx) {
+  int d = (idx - a.sw0) & (a.N - 1);
+  if (d >= a.N / 2) d -= a.N;
+  return w * a.hop - (int64_t)d * a.osr;
+}
+
+// Where the pass goes on after accepting window w with start s: the smallest w' > w with
+// w' * hop >= s + frame_len - step / 2.  That bound is w * hop + (s - w * hop) + lead_q * hop +
+// lead_r, and |s - w * hop| <= step / 2, so the one division is of 32-bit values.
+__device__ __forceinline__ int64_t next_window(const FindArgs& a, int64_t w, int64_t s) {
+  const int c = a.lead_r + (int)(s - w * a.hop);
+  const int64_t wn = w + a.lead_q + (c / a.hop32 + (c % a.hop32 > 0));
+  return wn > w + 1 ? wn : w + 1;
+}
+
+// Words word0, word0 + nwaves, .. of the tile that starts at window `base` with nt windows,
+// by the calling wave: at most kWordsPerWave of them (nwaves >= kWaves - 1).  All loads of the
+// wave's words are issued before the first is used, so a tile costs one trip to memory, not
+// one per word.
+constexpr int kWordsPerWave = (kTileWords + kWaves - 2) / (kWaves - 1);
+
+__device__ __forceinline__ void build_tile(const FindArgs& a, const float* pw, const float* pa, const uint16_t* ix,
+                                           Tile& t, int64_t base, int nt, int word0, int nwaves, int lane) {
+  const int words = (nt + 63) >> 6;
+  float p0[kWordsPerWave], f0[kWordsPerWave], p1[kWordsPerWave], f1[kWordsPerWave];
+  int i0[kWordsPerWave], i1[kWordsPerWave];
+#pragma unroll
+  for (int u = 0; u < kWordsPerWave; ++u) {
+    const int rel = (word0 + u * nwaves) * 64 + lane;
+    p0[u] = f0[u] = p1[u] = f1[u] = 0.0f;
+    i0[u] = i1[u] = 0;
+    if (rel < nt) {
+      const int64_t w = base + rel;  // w + k < W
+      i0[u] = ix[w];
+      i1[u] = ix[w + a.k];
+      p0[u] = pw[w];
+      f0[u] = pa[w];
+      p1[u] = pw[w + a.k];
+      f1[u] = pa[w + a.k];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < kWordsPerWave; ++u) {
+    const int word = word0 + u * nwaves, rel = word * 64 + lane;
+    if (word >= words) break;
+    const int64_t start = refined_start(a, base + rel, i0[u]);
+    const bool bit = rel < nt && p0[u] - f0[u] >= a.thresh && p1[u] - f1[u] >= a.thresh &&
+                     ((i1[u] - i0[u]) & (a.N - 1)) == a.dsync && start >= 0 && start <= a.last_start;
+    const unsigned long long m = __ballot(bit);
+    t.index[rel] = (uint16_t)i0[u];
+    if (lane == 0) t.mask[word] = m;
+  }
+}
+
+struct Pass {
+  int64_t first, w;  // no frame starts before `first`; the next window to test
+  int64_t cnt;
+};
+
+// v of lane l, the same l in every lane.
+__device__ __forceinline__ unsigned long long lane_value(unsigned long long v, int l) {
+  l = __builtin_amdgcn_readfirstlane(l);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// The successor of every set bit of a built tile (windows wave0 * 64 + lane, + nwaves * 64, ..):
+// succ[rel] = the tile-relative window the pass accepts after accepting rel, or kNoSucc.
+__device__ __forceinline__ void link_tile(const FindArgs& a, const Tile& t, uint16_t* succ, int64_t base, int nt,
+                                          int wave0, int nwaves, int lane) {
+  const int words = (nt + 63) >> 6;
+  for (int rel = wave0 * 64 + lane; rel < nt; rel += nwaves * 64) {
+    if (((t.mask[rel >> 6] >> (rel & 63)) & 1ull) == 0ull) continue;
+    const int64_t w = base + rel, s = refined_start(a, w, t.index[rel]), first = s + a.frame_len;
+    const int64_t wn = next_window(a, w, s);  // > w
+    unsigned res = kNoSucc;
+    if (wn < base + nt) {
+      int word = (int)(wn - base) >> 6;
+      unsigned long long b = t.mask[word] & (~0ull << ((int)(wn - base) & 63));
+      for (;;) {  // every turn clears a bit or moves to the next word
+        while (b != 0ull && res == kNoSucc) {
+          const int u = word * 64 + __ffsll((long long)b) - 1;
+          if (refined_start(a, base + u, t.index[u]) >= first) res = (unsigned)u;
+          b &= b - 1;
+        }
+        if (res != kNoSucc || ++word >= words) break;
+        b = t.mask[word];
+      }
+    }
+    succ[rel] = (uint16_t)res;
+  }
+}
+
+// The first window of the tile the pass accepts from its state p (tile-relative), or -1 with
+// the position moved to the tile's end.  One whole wave, uniform state; p.w >= base.
+__device__ __forceinline__ int first_in_tile(const FindArgs& a, const Tile& t, int64_t base, int nt, Pass& p,
+                                             int lane) {
+  const int words = (nt + 63) >> 6;
+  const int64_t stop = base + nt;
+  while (p.w < stop) {
+    // mask words wb .. wb + 63, one per lane, wb the position's word; the block ends at `bend`
+    const int wb = (int)(p.w - base) >> 6;
+    const unsigned long long m = wb + lane < words ? t.mask[wb + lane] : 0ull;
+    const int64_t bfull = base + (int64_t)(wb + 64) * 64;
+    const int64_t bend = bfull < stop ? bfull : stop;  // > p.w
+    while (p.w < bend) {
+      // the next non-empty word of the block from the position on (bits below it cleared)
+      const int rel = (int)(p.w - base), j0 = (rel >> 6) - wb;
+      unsigned long long mm = lane < j0 ? 0ull : m;
+      if (lane == j0) mm &= ~0ull << (rel & 63);
+      const unsigned long long nz = __ballot(mm != 0ull);
+      if (nz == 0ull) {
+        p.w = bend;
+        break;
+      }
+      const int j = __ffsll((long long)nz) - 1;
+      const unsigned long long bits = lane_value(mm, j);
+      const int word = wb + j;
+      // lane l: window word * 64 + l of the tile
+      const int64_t start = refined_start(a, base + (int64_t)word * 64 + lane, t.index[word * 64 + lane]);
+      const unsigned long long ok = __ballot(((bits >> lane) & 1ull) != 0ull && start >= p.first);
+      if (ok != 0ull) return word * 64 + __ffsll((long long)ok) - 1;  // >= p.w - base
+      const int64_t nw = base + (int64_t)(word + 1) * 64;  // > p.w, <= bfull
+      p.w = nw < stop ? nw : stop;
+    }
+  }
+  return -1;
+}
+
+// The greedy pass over one built and linked tile, by one whole wave (all 64 lanes, uniform
+// state): the first frame by search, the rest by their successors.
+__device__ __forceinline__ void walk_tile(const FindArgs& a, const Tile& t, const uint16_t* succ, int64_t base,
+                                          int nt, int64_t* starts, Pass& p, int lane) {
+  int rel = first_in_tile(a, t, base, nt, p, lane);
+  if (rel < 0) return;
+  const int64_t stop = base + nt;
+  for (;;) {  // rel grows with every turn and stays below nt
+    const int64_t w = base + rel, s = refined_start(a, w, t.index[rel]);
+    const unsigned nx = succ[rel];
+    if (lane == 0 && p.cnt < a.capacity) starts[p.cnt] = s;
+    ++p.cnt;
+    p.first = s + a.frame_len;
+    if (nx == kNoSucc) {
+      // nothing more in this tile: on from the jump, or from the next tile if that is later
+      const int64_t wn = next_window(a, w, s);
+      p.w = wn > stop ? wn : stop;
+      return;
+    }
+    rel = (int)nx;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) k_find_frames(FindArgs a) {
+  __shared__ Tile tiles[3];
+  __shared__ uint16_t succ[2][kFindTile];
+  __shared__ int64_t done;  // the row's count, for the fill
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t row = blockIdx.x;
+  const float* pw = a.power + row * a.stride;
+  const float* pa = a.power_avg + row * a.stride;
+  const uint16_t* ix = a.index + row * a.stride;
+  int64_t* starts = a.starts + row * a.capacity;
+
+  Pass p;
+  p.first = a.first ? a.first[row] : 0;
+  p.cnt = 0;
+  // ceil(max(first - step / 2, 0) / hop), kept within the windows there are
+  const int64_t lead = p.first > a.half_step ? p.first - a.half_step : 0;
+  p.w = lead / a.hop + (lead % a.hop != 0);
+  const int64_t n = a.n > 0 ? a.n : 0;
+  if (p.w > n) p.w = n;
+
+  const int64_t t0 = p.w / kFindTile, t1 = (n + kFindTile - 1) / kFindTile;  // tiles t0 .. t1 - 1
+  const auto windows = [n](int64_t t) {  // of tile t < t1
+    const int64_t left = n - t * kFindTile;
+    return left < kFindTile ? (int)left : kFindTile;
+  };
+  // tile t is built into tiles[t % 3] and linked into succ[t & 1]
+  if (t0 < t1) build_tile(a, pw, pa, ix, tiles[t0 % 3], t0 * kFindTile, windows(t0), wave, kWaves, lane);
+  __syncthreads();
+  if (t0 < t1) {
+    link_tile(a, tiles[t0 % 3], succ[t0 & 1], t0 * kFindTile, windows(t0), wave, kWaves, lane);
+    if (t0 + 1 < t1)
+      build_tile(a, pw, pa, ix, tiles[(t0 + 1) % 3], (t0 + 1) * kFindTile, windows(t0 + 1), wave, kWaves, lane);
+  }
+  __syncthreads();
+  for (int64_t t = t0; t < t1; ++t) {
+    if (wave == 0) {
+      walk_tile(a, tiles[t % 3], succ[t & 1], t * kFindTile, windows(t), starts, p, lane);
+    } else {
+      // (tiles[(t + 2) % 3] was last read while tile t - 1 was walked, succ[(t + 1) & 1] too)
+      if (t + 2 < t1)
+        build_tile(a, pw, pa, ix, tiles[(t + 2) % 3], (t + 2) * kFindTile, windows(t + 2), wave - 1, kWaves - 1,
+                   lane);
+      if (t + 1 < t1)
+        link_tile(a, tiles[(t + 1) % 3], succ[(t + 1) & 1], (t + 1) * kFindTile, windows(t + 1), wave - 1,
+                  kWaves - 1, lane);
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    done = p.cnt;
+    a.count[row] = (int32_t)p.cnt;  // cnt <= n < 2^31
+    a.end[row] = p.first;
+  }
+  __syncthreads();
+  for (int64_t i = (done < a.capacity ? done : a.capacity) + tid; i < a.capacity; i += kThreads) starts[i] = -1;
+}
+
+}  // namespace
+}  // namespace lora
+
+using lora::set_last_error;
+
+extern "C" {
+
+int64_t lora_find_frames_tile(void) { return lora::kFindTile; }
+
+int64_t lora_find_frames_batch(const lora_find_params* p, const float* power, const float* power_avg,
+                               const uint16_t* index, int64_t rows, int64_t W, int64_t stride, const int64_t* first,
+                               int64_t row_len, int64_t capacity, int64_t* starts, int32_t* count, int64_t* end,
+                               void* stream) {
+  if (!p) return set_last_error(LORA_EINVAL, "null params");
+  if (p->sf < 6 || p->sf > 12) return set_last_error(LORA_EINVAL, "the frame finder needs SF 6-12");
+  if (p->osr < 1 || p->osr > (1u << 16)) return set_last_error(LORA_EINVAL, "osr must be in 1..65536");
+  const int64_t N = int64_t(1) << p->sf, step = N * (int64_t)p->osr;
+  if (p->hop < 1 || step % p->hop != 0 || step / p->hop < 2)
+    return set_last_error(LORA_EINVAL, "hop must divide step = N * osr at least twice");
+  if (p->frame_symbols < 0 || p->frame_symbols >= (int64_t(1) << 31))
+    return set_last_error(LORA_EINVAL, "frame_symbols must be in 0 .. 2^31 - 1");
+  if (rows < 0 || W < 0 || stride < 0 || row_len < 0 || capacity < 0)
+    return set_last_error(LORA_EINVAL, "negative rows / W / stride / row_len / capacity");
+  if (W >= (int64_t(1) << 31)) return set_last_error(LORA_EINVAL, "W must be < 2^31");
+  if (rows >= (int64_t(1) << 31)) return set_last_error(LORA_EINVAL, "batch too large");
+  if (rows > 1 && stride < W) return set_last_error(LORA_EINVAL, "stride smaller than windows per row");
+  if (rows == 0) return 0;
+  if (!count || !end || (capacity > 0 && !starts)) return set_last_error(LORA_EINVAL, "null output");
+  const int64_t k = step / p->hop;
+  if (W > k && (!power || !power_avg || !index)) return set_last_error(LORA_EINVAL, "null metrics");
+  lora::FindArgs a{};
+  a.power = power;
+  a.power_avg = power_avg;
+  a.index = index;
+  a.first = first;
+  a.starts = starts;
+  a.count = count;
+  a.end = end;
+  a.stride = stride;
+  a.capacity = capacity;
+  a.n = W - k;
+  a.hop = p->hop;
+  a.osr = p->osr;
+  a.half_step = step / 2;
+  a.frame_len = (p->frame_symbols + 2) * step;
+  a.last_start = row_len - a.frame_len;
+  a.lead_q = (a.frame_len - a.half_step) / p->hop;
+  a.lead_r = (int)((a.frame_len - a.half_step) % p->hop);
+  a.hop32 = (int)p->hop;  // hop <= step / 2 <= 2^27
+  a.k = (int)k;
+  a.N = (int)N;
+  const int sync = (int)(p->sync & 0xFFu);
+  a.sw0 = (sync >> 4) << (p->sf - 4);
+  const int sw1 = (sync & 15) << (p->sf - 4);
+  a.dsync = (sw1 - a.sw0) & (a.N - 1);
+  a.thresh = p->thresh_db;
+  int prev = 0;
+  hipError_t e = hipGetDevice(&prev);
+  if (e == hipSuccess && prev != p->device) e = hipSetDevice(p->device);
+  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("find device: ") + hipGetErrorString(e));
+  hipLaunchKernelGGL(lora::k_find_frames, dim3((unsigned)rows), dim3(lora::kThreads), 0,
+                     static_cast<hipStream_t>(stream), a);
+  e = hipGetLastError();
+  if (prev != p->device) hipSetDevice(prev);
+  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("k_find_frames: ") + hipGetErrorString(e));
+  return rows;
+}
+
+}  // extern "C"

@@ -43,6 +43,8 @@ EXPORTED_SYMBOLS = (
     "lora_demod_soft_bits_batch",
     "lora_detect_scan_windows",
     "lora_detect_scan_batch",
+    "lora_find_frames_tile",
+    "lora_find_frames_batch",
     "lora_channelize_outputs",
     "lora_channelize_batch",
     "lora_resample_outputs",
@@ -108,6 +110,25 @@ class SymbolMetrics(C.Structure):
     ]
 
 
+class FindParams(C.Structure):
+    """lora_find_params: the frame finder's geometry, threshold and device."""
+
+    _fields_ = [
+        ("sf", C.c_uint),
+        ("osr", C.c_uint),
+        ("sync", C.c_uint),
+        ("thresh_db", C.c_float),
+        ("hop", C.c_int64),
+        ("frame_symbols", C.c_int64),
+        ("device", C.c_int),
+    ]
+
+
+# windows per tile of the finder kernel's pass (lora_find_frames_tile; tests/test_find_capi.py
+# holds the two together)
+FIND_TILE = 4096
+
+
 class LoraError(RuntimeError):
     """Raised for negative return codes of the C-ABI (reference: -1 / 0 returns)."""
 
@@ -153,6 +174,13 @@ def lib() -> C.CDLL:
     L.lora_detect_scan_batch.restype = C.c_int64
     L.lora_detect_scan_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                          C.POINTER(SymbolMetrics), C.c_void_p]
+    # the frame finder (csrc/lora_find.hip)
+    L.lora_find_frames_tile.restype = C.c_int64
+    L.lora_find_frames_tile.argtypes = []
+    L.lora_find_frames_batch.restype = C.c_int64
+    L.lora_find_frames_batch.argtypes = [C.POINTER(FindParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
     # the down-converter bank (csrc/lora_channelize.hip)
     L.lora_channelize_outputs.restype = C.c_int64
     L.lora_channelize_outputs.argtypes = [C.c_int64, C.c_int64, C.c_int64]

@@ -509,6 +509,35 @@ class LoRaDemod:
         self.last = res
         return channel, starts, res.symbols[:, :self.mtu]
 
+    def work_stream_device(self, iq: torch.Tensor, frame_symbols: int, hop: Optional[int] = None,
+                           thresh_db: float = 0.0, first=None, capacity: Optional[int] = None):
+        """``work_stream`` without the host (``lora_phy_amd.stream.receive_device`` with this block's
+        plan and sync word): a [L] stream or [R, L] rows.  Returns ``(found, symbols[:, :, :mtu])``
+        - the stream.FoundFrames (count [R], starts [R, capacity], end [R]) and the data symbols of
+        every slot, [R, capacity, <= mtu]; only the slots of ``found.valid`` hold a frame.  ``last``
+        keeps the DemodResult of all ``R * capacity`` slots.  Nothing synchronises."""
+        from . import stream
+
+        got = stream.receive_device(self.plan, iq, frame_symbols, hop, self.sync, thresh_db, first, capacity)
+        self.last = got.result
+        R, cap = got.found.starts.shape
+        return got.found, got.result.symbols.reshape(R, cap, got.result.symbols.shape[1])[:, :, :self.mtu]
+
+    def work_wideband_device(self, chan, iq: torch.Tensor, frame_symbols: int, hop: Optional[int] = None,
+                             thresh_db: float = 0.0, scale: Optional[float] = None, first=None,
+                             capacity: Optional[int] = None):
+        """``work_wideband`` without the host (``lora_phy_amd.stream.receive_wideband_device`` with
+        this block's plan and sync word).  Returns ``(found, symbols[:, :, :mtu])`` as
+        ``work_stream_device`` does, row r being channel r and starts in channel samples; ``last``
+        keeps the DemodResult of all ``C * capacity`` slots.  Nothing synchronises."""
+        from . import stream
+
+        got = stream.receive_wideband_device(self.plan, chan, iq, frame_symbols, hop, self.sync, thresh_db, scale,
+                                             first, capacity)
+        self.last = got.result
+        R, cap = got.found.starts.shape
+        return got.found, got.result.symbols.reshape(R, cap, got.result.symbols.shape[1])[:, :, :self.mtu]
+
     def sync_ok(self) -> torch.Tensor:
         """Per-frame flag: recovered sync word equals the configured one."""
         if self.last is None:

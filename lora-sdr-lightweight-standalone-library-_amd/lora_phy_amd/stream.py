@@ -33,6 +33,15 @@ symbol a candidate.  No detection-probability figure is claimed, because none ha
 measured.  A perfectly aligned noiseless window has no noise floor (``power_avg = -inf``, so
 ``snr = +inf`` and it passes any threshold); a silent window gives NaN and never passes.
 
+The finder on the device.  ``find_frames`` computes the candidates on the device, copies every
+window's packed start to the host and runs the greedy pass there: one synchronisation per call,
+the only one of ``receive``.  ``find_frames_device`` is the same rule as one kernel
+(lora_find_frames_batch, csrc/lora_find.hip): the accepted starts of every row stay on the
+device, in a fixed number of slots per row with a count beside them (``FoundFrames``), and
+``receive_device`` / ``receive_wideband_device`` demodulate all the slots without ever reading
+device memory on the host - so the next chunk can be enqueued before anyone looks at this one's
+count.  The outputs equal the host finder's as integers.
+
 Wideband captures.  An SDR delivers one wideband stream that holds several LoRa channels at
 known offsets from the tuner frequency.  ``Channelizer`` is the stage in front of the scan: one
 kernel mixes every channel down, low-pass filters and decimates it (lora_channelize_batch; the
@@ -71,7 +80,8 @@ spectral-mask or adjacent-channel figure is claimed.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from dataclasses import dataclass
+from typing import Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -80,7 +90,8 @@ from . import _capi
 from .demod import DemodPlan, DemodResult, DetectMetrics, _check_iq, _require_cuda, _stream_handle
 
 __all__ = ["find_frames", "extract_frames", "receive", "lowpass_taps", "nco_table", "Channelizer",
-           "receive_wideband", "raw_scale", "raw_to_complex", "Synthesizer", "transmit_wideband"]
+           "receive_wideband", "raw_scale", "raw_to_complex", "Synthesizer", "transmit_wideband",
+           "FoundFrames", "StreamFrames", "find_frames_device", "receive_device", "receive_wideband_device"]
 
 _NONE = -(1 << 62)  # "no candidate here" in the packed starts
 
@@ -509,6 +520,205 @@ def receive_wideband(plan: DemodPlan, chan: Channelizer, iq: torch.Tensor, frame
     frames = _gather(rows.reshape(-1), channel_t * Wc + starts_t, frame_len)
     return channel_t, starts_t, plan.run(frames)
 
+
+
+@dataclass
+class FoundFrames:
+    """What ``find_frames_device`` leaves on the device for R rows with ``capacity`` slots each."""
+
+    count: torch.Tensor   # [R] int32            frames the pass accepted (may exceed capacity)
+    starts: torch.Tensor  # [R, capacity] int64  the first min(count, capacity) starts, then -1
+    end: torch.Tensor     # [R] int64            ``first`` as the pass left it: the next chunk's, once shifted
+
+    @property
+    def valid(self) -> torch.Tensor:
+        """bool [R, capacity]: ``arange(capacity) < count[:, None]`` - the slots that hold a frame."""
+        return torch.arange(self.starts.shape[1], device=self.count.device) < self.count[:, None]
+
+
+@dataclass
+class StreamFrames:
+    """``receive_device``'s result: the found frames and the demodulation of every slot,
+    ``result`` having ``F = R * capacity`` frames in row-major order (slot j of row r is frame
+    ``r * capacity + j``).  Only the slots of ``found.valid`` mean anything."""
+
+    found: FoundFrames
+    result: DemodResult
+
+
+def _find_first(first, R: int, dev: torch.device) -> Optional[torch.Tensor]:
+    """``first`` as the entry takes it: None (0 in every row) or an int64 [R] tensor."""
+    if first is None:
+        return None
+    if isinstance(first, torch.Tensor):
+        if first.dtype != torch.int64:
+            raise TypeError(f"first must be an int64 tensor, got {first.dtype}")
+        if first.dim() != 1 or first.shape[0] != R:
+            raise ValueError(f"first must be one int per row: an int64 [{R}] tensor")
+        return first
+    first = int(first)
+    if first < 0:
+        raise ValueError("first must be >= 0")
+    return torch.full((R,), first, dtype=torch.int64, device=dev) if first and R else None
+
+
+def find_frames_device(metrics: DetectMetrics, hop: int, sf: int, osr: int, frame_symbols: int, sync: int = 0x12,
+                       thresh_db: float = 0.0, first: Union[None, int, torch.Tensor] = None,
+                       row_len: Optional[int] = None, capacity: Optional[int] = None,
+                       out: Optional[FoundFrames] = None, bw: int = 125000) -> FoundFrames:
+    """``find_frames`` as one kernel (lora_find_frames_batch): the frame starts of every scanned row
+    by the rule in this module's docstring, left on the device.  Nothing is copied to the host
+    and nothing synchronises.
+
+    ``metrics``: ``DemodPlan.scan``'s CUDA result for one row ([W]) or R rows ([R, W]; rows may be
+    strided as ``scan``'s ``out=`` allows, power, power_avg and index sharing one row stride).
+    ``first``: no frame starts before this sample - None (0), an int for every row, or an int64
+    [R] tensor on the metrics' device, which is how a chunked caller carries the previous chunk's
+    ``end`` without reading it.  ``row_len`` as for ``find_frames``.  ``capacity``: slots per row
+    (default ``row_len // frame_len``, which bounds what a row can hold, so nothing is dropped);
+    with a smaller one ``count`` still counts every accepted frame and ``count > capacity`` tells
+    that some were not stored.  ``out``: a FoundFrames of contiguous tensors to write into (count
+    int32 [R], starts int64 [R, capacity], end int64 [R]).
+
+    Returns FoundFrames (R = 1 for a [W] input).  All of it is fully written, also for rows with
+    no window to test (count 0, ``end = first``).  One kernel on the current stream; nothing is
+    allocated besides the outputs and, for an int ``first`` other than 0, its [R] tensor.
+    ``ValueError``: as ``find_frames``, and a ``first`` tensor that is not [R]; ``TypeError``: a
+    ``first`` tensor that is not int64, metrics of the wrong dtype or not on a CUDA device."""
+    N, step, k, sw0, sw1, frame_len = _geometry(hop, sf, osr, frame_symbols, sync, bw)
+    hop, osr = int(hop), step // N
+    power, floor, index = metrics.power, metrics.power_avg, metrics.index
+    if not all(isinstance(t, torch.Tensor) for t in (power, floor, index)):
+        raise TypeError("find_frames_device needs metrics with power, power_avg and index")
+    if power.dim() == 1:
+        power, floor, index = power.unsqueeze(0), floor.unsqueeze(0), index.unsqueeze(0)
+    if power.dim() != 2 or floor.shape != power.shape or index.shape != power.shape:
+        raise ValueError("find_frames_device takes power, power_avg and index of one [W] or [R, W] shape")
+    if power.dtype != torch.float32 or floor.dtype != torch.float32 or index.dtype != torch.uint16:
+        raise TypeError("power and power_avg must be float32 and index uint16")
+    R, W = power.shape
+    first_t = _find_first(first, R, power.device)
+    if row_len is None:
+        row_len = (W - 1) * hop + step if W else 0
+    row_len = int(row_len)
+    capacity = row_len // frame_len if capacity is None else int(capacity)
+    if row_len < 0 or capacity < 0:
+        raise ValueError("row_len and capacity must be >= 0")
+    for t, name in ((power, "power"), (floor, "power_avg"), (index, "index")):
+        _require_cuda(t, "metrics." + name)
+    dev = power.device
+    if floor.device != dev or index.device != dev or (first_t is not None and first_t.device != dev):
+        raise ValueError(f"power_avg, index and first must be on {dev}, where power is")
+    if W > 1 and any(t.stride(1) != 1 for t in (power, floor, index)):
+        raise ValueError("the metrics must have unit column stride")
+    strides = {t.stride(0) for t in (power, floor, index)} if R > 1 else {W}
+    if len(strides) != 1 or min(strides) < W:
+        raise ValueError("power, power_avg and index must share one row stride >= W")
+    if out is None:
+        out = FoundFrames(count=torch.empty(R, dtype=torch.int32, device=dev),
+                          starts=torch.empty((R, capacity), dtype=torch.int64, device=dev),
+                          end=torch.empty(R, dtype=torch.int64, device=dev))
+    else:
+        for name, dt, shape in (("count", torch.int32, (R,)), ("starts", torch.int64, (R, capacity)),
+                                ("end", torch.int64, (R,))):
+            t = getattr(out, name)
+            _require_cuda(t, "out." + name)
+            if t.dtype != dt:
+                raise TypeError(f"out.{name} must be {dt}, got {t.dtype}")
+            if t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"out.{name} must be a contiguous {dt} {list(shape)} tensor on {dev}")
+    if R == 0:
+        return out
+    if first_t is not None and not first_t.is_contiguous():
+        first_t = first_t.contiguous()
+    prm = _capi.FindParams(int(sf), osr, int(sync) & 0xFF, float(thresh_db), hop, int(frame_symbols), dev.index)
+    got = _capi.check(_capi.lib().lora_find_frames_batch(
+        _capi.C.byref(prm), power.data_ptr(), floor.data_ptr(), index.data_ptr(), R, W, strides.pop(),
+        first_t.data_ptr() if first_t is not None else None, row_len, capacity,
+        out.starts.data_ptr() if capacity else None, out.count.data_ptr(), out.end.data_ptr(), _stream_handle(dev)))
+    assert got == R, (got, R)
+    return out
+
+
+def _receive_rows(plan: DemodPlan, rows: torch.Tensor, frame_symbols, hop, sync, thresh_db, first,
+                  capacity) -> StreamFrames:
+    """Scan, find, gather and demodulate the [R, L] rows (checked by the caller) on the device."""
+    hop = plan.step // 4 if hop is None else int(hop)
+    frame_len = _geometry(hop, plan.sf, plan.osr, frame_symbols, sync, plan.bw)[-1]
+    R, L = rows.shape
+    dev = plan.device
+    if L >= plan.step:
+        met = plan.scan(rows, hop)
+    else:  # (no window: nothing to scan, and the finder only has its outputs to fill)
+        met = DetectMetrics(*(torch.empty((R, 0), dtype=dt, device=dev)
+                              for dt in (torch.float32, torch.float32, torch.float32, torch.uint16)))
+    found = find_frames_device(met, hop, plan.sf, plan.osr, frame_symbols, sync, thresh_db, first, L, capacity,
+                               None, plan.bw)
+    cap = found.starts.shape[1]
+    if R * cap == 0:
+        return StreamFrames(found, _no_frames(frame_symbols, dev))
+    if L < frame_len:
+        raise ValueError(f"rows of {L} samples hold no frame of {frame_len}: capacity must be 0")
+    # the rows as one stream (row r begins at r * row stride); an empty slot (-1) reads its row's
+    # first frame_len samples
+    rs = rows.stride(0) if R > 1 else L
+    flat = rows.as_strided(((R - 1) * rs + L,), (1,))
+    at = found.starts.clamp_min(0) + (torch.arange(R, device=dev) * rs)[:, None]
+    return StreamFrames(found, plan.run(_gather(flat, at.reshape(-1), frame_len)))
+
+
+def receive_device(plan: DemodPlan, iq: torch.Tensor, frame_symbols: int, hop: Optional[int] = None,
+                   sync: int = 0x12, thresh_db: float = 0.0, first: Union[None, int, torch.Tensor] = None,
+                   capacity: Optional[int] = None) -> StreamFrames:
+    """``receive`` without the host: ``plan.scan``, ``find_frames_device``, one gather and one
+    ``plan.run``, with nothing read back in between - no synchronisation, every shape computed
+    from host integers.  ``iq`` is a [L] stream or [R, L] rows (complex64 CUDA, rows laid out as
+    ``scan`` takes them); ``first`` and ``capacity`` are ``find_frames_device``'s, ``row_len`` is L.
+
+    Returns StreamFrames: ``found`` (count [R], starts [R, capacity], end [R]) and ``result``, the
+    DemodResult of ALL ``R * capacity`` slots, row-major.  The slots of ``found.valid`` hold what
+    ``receive`` returns for the same stream, bit for bit.  A slot beyond its row's count holds
+    the demodulation of the row's first ``frame_len`` samples: defined input, nothing
+    uninitialised is read, and the result means nothing - select with ``found.valid``.
+    (``symbols`` is uint16, which torch does not index on the device: select from
+    ``symbols.to(torch.int32)``, or after the copy to the host.)
+
+    ``capacity`` defaults to ``L // frame_len``, so the gathered frames are as large as the
+    stream itself and every slot is demodulated; a caller who knows their traffic passes a
+    smaller one and watches ``found.count > capacity`` for frames that were found but not kept.
+    A row shorter than ``frame_len`` gives capacity 0 and no demod call.  Chunked: the next
+    chunk's ``first`` is ``(found.end - advance).clamp_min(0)``, a tensor operation, so chunk b + 1
+    can be enqueued before anyone reads chunk b's count."""
+    if not plan.dechirp:
+        raise ValueError("receive_device needs a plan with dechirp=True: the finder reads dechirped peaks")
+    if not isinstance(iq, torch.Tensor) or iq.dim() not in (1, 2):
+        raise ValueError("receive_device takes one [L] stream or [R, L] rows")
+    hop = plan.step // 4 if hop is None else int(hop)
+    _geometry(hop, plan.sf, plan.osr, frame_symbols, sync, plan.bw)
+    return _receive_rows(plan, _check_iq(iq, plan.device), frame_symbols, hop, sync, thresh_db, first, capacity)
+
+
+def receive_wideband_device(plan: DemodPlan, chan: "Channelizer", iq: torch.Tensor, frame_symbols: int,
+                            hop: Optional[int] = None, sync: int = 0x12, thresh_db: float = 0.0,
+                            scale: Optional[float] = None, first: Union[None, int, torch.Tensor] = None,
+                            capacity: Optional[int] = None) -> StreamFrames:
+    """``receive_wideband`` without the host: ``chan.run`` on the [L] complex64 stream (or the raw
+    [L, 2] integer stream, converted with ``scale``), then ``receive_device`` over the [C, Wc]
+    channel rows - row r of the result is channel r, slot j of channel r is frame ``r * capacity +
+    j`` of ``result``.  Starts are in CHANNEL samples, as ``receive_wideband``'s; ``first`` ([C], in
+    channel samples) and ``capacity`` are ``find_frames_device``'s with ``row_len = Wc``.  The valid
+    slots, taken channel by channel, are ``receive_wideband``'s frames in its order.  No
+    synchronisation; everything said of ``receive_device``'s slots and capacity holds here."""
+    if not plan.dechirp:
+        raise ValueError("receive_wideband_device needs a plan with dechirp=True: the finder reads dechirped peaks")
+    if not isinstance(iq, torch.Tensor) or iq.dim() != (2 if _is_raw(iq) else 1):
+        raise ValueError("receive_wideband_device takes one [L] stream (raw samples: [L, 2])")
+    if chan.device != plan.device:
+        raise ValueError(f"the channelizer is on {chan.device}, the plan is on {plan.device}")
+    hop = plan.step // 4 if hop is None else int(hop)
+    _geometry(hop, plan.sf, plan.osr, frame_symbols, sync, plan.bw)
+    rows = chan.run(iq, scale=scale)  # [C, Wc]
+    return _receive_rows(plan, rows, frame_symbols, hop, sync, thresh_db, first, capacity)
 
 
 # raw output dtypes of the synthesis bank: the default inv_scale (exact in fp32)
