@@ -1091,6 +1091,28 @@ struct lora_demod_plan {
 namespace {
 
 // Event pair around one kernel launch (profiling only; no-op when disabled).
+// The kernel arguments every plan entry starts from: value-initialised, with the rows' geometry
+// (`len` samples, `stride` apart) and the plan's constants and tables filled in.  The entry sets
+// what is its own: mode, dechirp, total, have_sync, est_only, the outputs and the workspace.
+KArgs plan_kargs(const lora_demod_plan* plan, const float* iq, int64_t len, int64_t stride) {
+  KArgs a{};
+  a.iq = reinterpret_cast<const cf*>(iq);
+  a.frame_len = len;
+  a.frame_stride = stride;
+  a.sf = (int)plan->prm.sf;
+  a.N = plan->N;
+  a.osr = (int)plan->prm.osr;
+  a.step = plan->step;
+  a.hann = plan->prm.window == LORA_WINDOW_HANN;
+  a.power_scale = plan->power_scale;
+  a.tw = plan->tw;
+  a.rev = plan->rev;
+  a.win = plan->win;
+  a.down = plan->down;
+  a.down1 = plan->down1;
+  return a;
+}
+
 struct ProfScope {
   lora_demod_plan* plan;
   hipStream_t st;
@@ -1226,14 +1248,10 @@ int lora_demod_plan_create(const lora_demod_params* params, lora_demod_plan** ou
   auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   const size_t total = al(b_tw) + al(b_down) + al(b_down1) + al(b_win) + al(b_rev) + al(b_twT) + 256;
 
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  HIP_TRY(hipSetDevice(p.device));
+  lora::DeviceGuard guard(p.device);
+  if (guard.err != hipSuccess) return lora::hip_error("plan device", guard.err);
   void* mem = nullptr;
-  if (hipMalloc(&mem, total) != hipSuccess) {
-    hipSetDevice(prev);
-    return set_error(LORA_ENOMEM, "hipMalloc of plan tables failed");
-  }
+  if (hipMalloc(&mem, total) != hipSuccess) return set_error(LORA_ENOMEM, "hipMalloc of plan tables failed");
   unsigned char* b = static_cast<unsigned char*>(mem);
   lora_demod_plan* plan = new lora_demod_plan();
   plan->prm = p;
@@ -1271,7 +1289,6 @@ int lora_demod_plan_create(const lora_demod_params* params, lora_demod_plan** ou
   if (e == hipSuccess) e = hipMemcpy(plan->rev, rev.data(), b_rev, hipMemcpyHostToDevice);
   if (e == hipSuccess && !twT.empty()) e = hipMemcpy(twT_dev, twT.data(), b_twT, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(plan->spec_fix, 0, sizeof(unsigned int));
-  hipSetDevice(prev);
   if (e != hipSuccess) {
     const std::string msg = std::string("plan setup: ") + hipGetErrorString(e);
     lora_demod_plan_destroy(plan);  // the tables
@@ -1289,9 +1306,8 @@ int lora_demod_plan_set_pipeline(lora_demod_plan* plan, int speculative) {
 
 int lora_demod_profile_enable(lora_demod_plan* plan, int max_calls) {
   if (!plan || max_calls < 0) return set_error(LORA_EINVAL, "bad argument");
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  HIP_TRY(hipSetDevice(plan->prm.device));
+  lora::DeviceGuard guard(plan->prm.device);
+  if (guard.err != hipSuccess) return lora::hip_error("profile device", guard.err);
   for (auto& r : plan->prof_recs) {
     hipEventDestroy(r.b);
     hipEventDestroy(r.e);
@@ -1303,7 +1319,6 @@ int lora_demod_profile_enable(lora_demod_plan* plan, int max_calls) {
   plan->prof_max = max_calls;
   plan->prof_calls = 0;
   plan->prof_short = false;
-  HIP_TRY(hipSetDevice(prev));
   return LORA_OK;
 }
 
@@ -1323,16 +1338,13 @@ int lora_demod_profile_read(lora_demod_plan* plan, float* stage_ms, int* calls) 
 
 int lora_demod_plan_destroy(lora_demod_plan* plan) {
   if (!plan) return LORA_OK;
-  int prev = 0;
-  hipGetDevice(&prev);
-  hipSetDevice(plan->prm.device);
+  lora::DeviceGuard guard(plan->prm.device);  // best effort: the plan is freed whatever guard.err says
   for (auto& r : plan->prof_recs) {
     hipEventDestroy(r.b);
     hipEventDestroy(r.e);
   }
   for (hipEvent_t e : plan->prof_pool) hipEventDestroy(e);
   hipFree(plan->dev_tables);
-  hipSetDevice(prev);
   delete plan;
   return LORA_OK;
 }
@@ -1382,30 +1394,15 @@ int64_t lora_demod_batch(lora_demod_plan* plan, const float* iq, int64_t frames,
 
   const lora_demod_params& p = plan->prm;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  if (prev != p.device) HIP_TRY(hipSetDevice(p.device));
+  lora::DeviceGuard guard(p.device);
+  if (guard.err != hipSuccess) return lora::hip_error("demod device", guard.err);
 
   const int64_t total = frame_len / plan->step;
-  KArgs a;
-  a.iq = reinterpret_cast<const cf*>(iq);
-  a.frame_len = frame_len;
-  a.frame_stride = frame_stride;
-  a.sf = (int)p.sf;
-  a.N = plan->N;
-  a.osr = (int)p.osr;
-  a.step = plan->step;
+  KArgs a = plan_kargs(plan, iq, frame_len, frame_stride);
   a.total = (int)total;
   a.mode = p.mode;
   a.have_sync = (p.mode == LORA_MODE_API) ? 1 : (p.mode == LORA_MODE_LEGACY && total >= 2 ? 1 : 0);
   a.dechirp = (p.mode != LORA_MODE_API && p.dechirp) ? 1 : 0;
-  a.hann = p.window == LORA_WINDOW_HANN;
-  a.power_scale = plan->power_scale;
-  a.tw = plan->tw;
-  a.rev = plan->rev;
-  a.win = plan->win;
-  a.down = plan->down;
-  a.down1 = plan->down1;
   a.twTA = plan->twTA;
   a.twTB = plan->twTB;
   a.twTB2 = plan->twTB2;
@@ -1427,7 +1424,6 @@ int64_t lora_demod_batch(lora_demod_plan* plan, const float* iq, int64_t frames,
   a.cfo = out->cfo;
   a.toff = out->time_offset;
   a.max_amp = out->max_amp;
-  a.est_only = 0;
   a.fast_rot = (p.precision == LORA_PRECISION_FAST && p.mode != LORA_MODE_RAW) ? 1 : 0;
 
   const int s0 = a.have_sync ? 2 : 0;
@@ -1438,10 +1434,7 @@ int64_t lora_demod_batch(lora_demod_plan* plan, const float* iq, int64_t frames,
   a.mx_bpf = (p.mode == LORA_MODE_LEGACY && frame_len > 0) ? bpf : 0;
   // split evenly over the frame's blocks
   const int chunk = (int)((((frame_len + bpf - 1) / bpf) + 1) & ~int64_t(1));
-  if (frames * bpf >= (int64_t(1) << 31)) {
-    if (prev != p.device) hipSetDevice(prev);
-    return set_error(LORA_EINVAL, "batch too large");
-  }
+  if (frames * bpf >= (int64_t(1) << 31)) return set_error(LORA_EINVAL, "batch too large");
   int kernels = 0;
   int rc = LORA_OK;
   if (p.mode == LORA_MODE_RAW && lora::t_launch_record) lora::t_launch_record->bad = true;
@@ -1560,9 +1553,8 @@ int64_t lora_demod_batch(lora_demod_plan* plan, const float* iq, int64_t frames,
   plan->last_kernels = kernels;
   if (rc == LORA_OK) {
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = set_error(LORA_EIO, std::string("kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) rc = lora::hip_error("kernel launch", e);
   }
-  if (prev != p.device) hipSetDevice(prev);
   return rc < 0 ? rc : nsym;
 }
 
@@ -1651,9 +1643,8 @@ int64_t lora_mod_batch(unsigned sf, unsigned osr, unsigned bw_hz, float amplitud
   a.iq = reinterpret_cast<cf*>(iq);
   a.frames = frames;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  if (prev != device) HIP_TRY(hipSetDevice(device));
+  lora::DeviceGuard guard(device);
+  if (guard.err != hipSuccess) return lora::hip_error("mod device", guard.err);
   // (lora::launch: recorded instead when the C++ drop-in dispatches on its AQL queue)
   // k_mod_phase: long chirps (the speculative blocks, step >= 1024) over about 1024 waves
   // (frames per wave a power of two <= 64: fewer lanes per wave, fewer redone blocks);
@@ -1672,10 +1663,8 @@ int64_t lora_mod_batch(unsigned sf, unsigned osr, unsigned bw_hz, float amplitud
   if (frames <= kMfMaxFrames && mf_ok) {
     // few frames: a workgroup per frame, windows of whole chirps or exact chirp fractions;
     // long chirps from the configuration's run tables (built here on first use)
-    if (step >= kMfTabMin && !mod_run_table(a, (int)sf, st)) {
-      if (prev != device) hipSetDevice(prev);
+    if (step >= kMfTabMin && !mod_run_table(a, (int)sf, st))
       return set_error(LORA_EIO, "modulator run tables: " + g_last_error);
-    }
     const int64_t nwin = (per_frame + W - 1) / W;
     lora::launch(k_mod_frame, dim3((unsigned)frames), dim3(kMfThreads), 0, st, a, W, (int)nwin);
   } else {
@@ -1685,8 +1674,7 @@ int64_t lora_mod_batch(unsigned sf, unsigned osr, unsigned bw_hz, float amplitud
     lora::launch(k_mod_samples, dim3((unsigned)((chirps + per_block - 1) / per_block)), dim3(per_block), 0, st, a);
   }
   hipError_t e = hipGetLastError();
-  if (prev != device) hipSetDevice(prev);
-  if (e != hipSuccess) return set_error(LORA_EIO, std::string("mod launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return lora::hip_error("mod launch", e);
   return per_frame;
 }
 
@@ -1701,36 +1689,18 @@ int64_t lora_estimate_offsets_batch(lora_demod_plan* plan, const float* iq, int6
   if (frames == 0 || total == 0) return total;
   if (!iq) return set_error(LORA_EINVAL, "null iq");
   const lora_demod_params& p = plan->prm;
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  if (prev != p.device) HIP_TRY(hipSetDevice(p.device));
-  KArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.iq = reinterpret_cast<const cf*>(iq);
-  a.frame_len = frame_len;
-  a.frame_stride = frame_stride;
-  a.sf = (int)p.sf;
-  a.N = plan->N;
-  a.osr = (int)p.osr;
-  a.step = plan->step;
+  lora::DeviceGuard guard(p.device);
+  if (guard.err != hipSuccess) return lora::hip_error("estimate device", guard.err);
+  KArgs a = plan_kargs(plan, iq, frame_len, frame_stride);
   a.total = (int)total;
   a.mode = LORA_MODE_API;
-  a.hann = p.window == LORA_WINDOW_HANN;
-  a.power_scale = plan->power_scale;
-  a.tw = plan->tw;
-  a.rev = plan->rev;
-  a.win = plan->win;
-  a.down = plan->down;
-  a.down1 = plan->down1;
   a.cfo = cfo;
   a.toff = time_offset;
-  a.mx_bpf = 0;
   a.est_only = 1;
   hipLaunchKernelGGL(k_estimate, dim3((unsigned)frames), dim3(256), sizeof(cf) * plan->N,
                      static_cast<hipStream_t>(stream), a);
   hipError_t e = hipGetLastError();
-  if (prev != p.device) hipSetDevice(prev);
-  if (e != hipSuccess) return set_error(LORA_EIO, std::string("estimate launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return lora::hip_error("estimate launch", e);
   return total;
 }
 
@@ -1759,31 +1729,14 @@ int64_t lora_demod_metrics_batch(lora_demod_plan* plan, const float* iq, int64_t
       return set_error(LORA_EINVAL, "LEGACY metrics need the frames' max_amp array");
   }
   if (frames == 0 || total == 0 || !any) return total;
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  if (prev != p.device) HIP_TRY(hipSetDevice(p.device));
-  KArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.iq = reinterpret_cast<const cf*>(iq);
-  a.frame_len = frame_len;
-  a.frame_stride = frame_stride;
-  a.sf = (int)p.sf;
-  a.N = plan->N;
-  a.osr = (int)p.osr;
-  a.step = plan->step;
+  lora::DeviceGuard guard(p.device);
+  if (guard.err != hipSuccess) return lora::hip_error("metrics device", guard.err);
+  KArgs a = plan_kargs(plan, iq, frame_len, frame_stride);
   a.total = (int)total;
   a.mode = p.mode;
   a.dechirp = (p.mode != LORA_MODE_API && p.dechirp) ? 1 : 0;
-  a.hann = p.window == LORA_WINDOW_HANN;
-  a.power_scale = plan->power_scale;
-  a.tw = plan->tw;
-  a.rev = plan->rev;
-  a.win = plan->win;
-  a.down = plan->down;
-  a.down1 = plan->down1;
   const int rc = lora::launch_detect_metrics(a, cfo, time_offset, max_amp, *out, frames,
                                              static_cast<hipStream_t>(stream));
-  if (prev != p.device) hipSetDevice(prev);
   return rc < 0 ? rc : total;
 }
 
@@ -1812,30 +1765,14 @@ int64_t lora_demod_soft_bits_batch(lora_demod_plan* plan, const float* iq, int64
       return set_error(LORA_EINVAL, "LEGACY soft bits need the frames' max_amp array");
   }
   if (frames == 0 || total == 0 || !llr) return total;
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  if (prev != p.device) HIP_TRY(hipSetDevice(p.device));
-  KArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.iq = reinterpret_cast<const cf*>(iq);
-  a.frame_len = frame_len;
-  a.frame_stride = frame_stride;
-  a.sf = (int)p.sf;
-  a.N = plan->N;
-  a.osr = (int)p.osr;
-  a.step = plan->step;
+  lora::DeviceGuard guard(p.device);
+  if (guard.err != hipSuccess) return lora::hip_error("soft bits device", guard.err);
+  KArgs a = plan_kargs(plan, iq, frame_len, frame_stride);
   a.total = (int)total;
   a.mode = p.mode;
   a.dechirp = (p.mode != LORA_MODE_API && p.dechirp) ? 1 : 0;
-  a.hann = p.window == LORA_WINDOW_HANN;
-  a.tw = plan->tw;
-  a.rev = plan->rev;
-  a.win = plan->win;
-  a.down = plan->down;
-  a.down1 = plan->down1;
   const int rc = lora::launch_soft_bits(a, cfo, time_offset, max_amp, llr, llr_stride, frames,
                                         static_cast<hipStream_t>(stream));
-  if (prev != p.device) hipSetDevice(prev);
   return rc < 0 ? rc : total;
 }
 
@@ -1861,28 +1798,12 @@ int64_t lora_detect_scan_batch(lora_demod_plan* plan, const float* iq, int64_t r
   if (grid < 0) return set_error(LORA_EINVAL, "batch too large");
   if (grid > 0 && !iq) return set_error(LORA_EINVAL, "null iq");
   if (grid == 0 || !any) return W;
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  if (prev != p.device) HIP_TRY(hipSetDevice(p.device));
-  KArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.iq = reinterpret_cast<const cf*>(iq);
-  a.frame_len = row_len;
-  a.frame_stride = row_stride;
-  a.sf = (int)p.sf;
-  a.N = plan->N;
-  a.osr = (int)p.osr;
-  a.step = plan->step;
+  lora::DeviceGuard guard(p.device);
+  if (guard.err != hipSuccess) return lora::hip_error("scan device", guard.err);
+  KArgs a = plan_kargs(plan, iq, row_len, row_stride);
   a.mode = LORA_MODE_RAW;
   a.dechirp = p.dechirp ? 1 : 0;
-  a.hann = p.window == LORA_WINDOW_HANN;
-  a.power_scale = plan->power_scale;
-  a.tw = plan->tw;
-  a.rev = plan->rev;
-  a.win = plan->win;
-  a.down = plan->down;
   const int rc = lora::launch_detect_scan(a, *out, rows, hop, static_cast<hipStream_t>(stream));
-  if (prev != p.device) hipSetDevice(prev);
   return rc < 0 ? rc : W;
 }
 
@@ -1898,17 +1819,15 @@ int64_t lora_compensate_offsets_batch(unsigned sf, unsigned osr, const float* in
   if (!in || !out || !cfo || !time_offset) return set_error(LORA_EINVAL, "null buffer");
   if (in == out) return set_error(LORA_EINVAL, "in and out must not overlap");
   const float Nosr = static_cast<float>(1u << sf) * static_cast<float>(osr);  // phy.cpp:156
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  if (prev != device) HIP_TRY(hipSetDevice(device));
+  lora::DeviceGuard guard(device);
+  if (guard.err != hipSuccess) return lora::hip_error("compensate device", guard.err);
   const int64_t n = frames * frame_len;
   hipLaunchKernelGGL(k_compensate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), reinterpret_cast<const cf*>(in),
                      reinterpret_cast<cf*>(out), frame_len, frame_stride, frames, Nosr, cfo,
                      time_offset);
   hipError_t e = hipGetLastError();
-  if (prev != device) hipSetDevice(prev);
-  if (e != hipSuccess) return set_error(LORA_EIO, std::string("compensate launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return lora::hip_error("compensate launch", e);
   return frame_len;
 }
 

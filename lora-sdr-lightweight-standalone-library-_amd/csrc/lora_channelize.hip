@@ -14,10 +14,11 @@
 // FIR's read of tap j for consecutive outputs (samples decim apart) is a read of consecutive
 // LDS entries.  The FIR runs from LDS, one output index per lane and two channels per lane at
 // a time; the taps are loaded 64 at a time, one per lane, and handed round by readlane.
-// tile is 64 where all channels fit the 64 KiB of LDS at once (channel_geometry below);
+// tile is 64 where all channels fit the 64 KiB of LDS at once (channel_geometry, csrc/lora_bank.h);
 // otherwise it shrinks to 32, 16 or 8, and if the channels still do not fit they are taken in
 // passes of `cg`, each pass re-reading the tile's samples (the ABI's extremes, 32 channels of
-// 512 taps at decim 64, run that way).
+// 512 taps at decim 64, run that way).  The mix stage, the oscillator's arithmetic, the geometry's
+// search and the argument rules are shared with the other banks: csrc/lora_bank.h.
 //
 // The kernel is a template over the sample format (csrc/lora_iq_format.h): complex64 for
 // lora_channelize_batch, cs16, cs8 and cu8 for lora_channelize_raw_batch, whose integer samples
@@ -27,9 +28,7 @@
 #include <string>
 
 #include "../../include/lora_mi355x.h"
-#include "lora_device.h"
-#include "lora_internal.h"
-#include "lora_iq_format.h"
+#include "lora_bank.h"
 
 #pragma clang fp contract(off)
 
@@ -37,9 +36,7 @@ namespace lora {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxTile = 64, kMinTile = 8;
-constexpr int kLdsSamples = 8192;  // mixed samples a workgroup holds: 64 KiB
-constexpr int kMaxTaps = 512, kMaxDecim = 64, kMaxPeriod = 4096, kMaxChannels = 32;
+constexpr int kMaxTaps = 512, kMaxDecim = 64;
 
 struct ChanArgs {
   const void* iq;  // samples of the kernel's format
@@ -54,28 +51,6 @@ struct ChanArgs {
   int steps[kMaxChannels];  // each in 0 .. period-1
   float scale;              // of an integer format's samples
 };
-
-// LDS entries of one channel: decim phase rows of `tile` outputs plus the taps' reach
-__host__ __device__ constexpr int channel_entries(int tile, int ntaps, int decim) {
-  return decim * (tile + (ntaps - 1) / decim);
-}
-
-// a / d and a % d for 0 <= a < 2^24, d <= 4096 and a / d < 2^13, inv = 1.0f / d: the product is
-// within a / d * 2^-23 < 1 of the quotient, so its truncation is off by at most one either way
-// (the products here are of 24-bit operands: __umul24 runs at full rate, a 32-bit multiply at a
-// quarter of it)
-__device__ __forceinline__ void divmod(unsigned a, unsigned d, float inv, unsigned& q, unsigned& r) {
-  q = (unsigned)((float)a * inv);
-  int rr = (int)a - (int)__umul24(q, d);
-  if (rr < 0) {
-    rr += (int)d;
-    --q;
-  } else if (rr >= (int)d) {
-    rr -= (int)d;
-    ++q;
-  }
-  r = (unsigned)rr;
-}
 
 template <int F>
 __global__ void __launch_bounds__(kThreads) k_channelize(ChanArgs a) {
@@ -100,25 +75,9 @@ __global__ void __launch_bounds__(kThreads) k_channelize(ChanArgs a) {
     const int nc = a.channels - c0 < a.cg ? a.channels - c0 : a.cg;
     if (c0) __syncthreads();  // the previous pass's FIR has read Z
 
-    // sample s of the tile, mixed for the pass's channels
-    auto mix = [&](int s, float xr, float xi) {
-      unsigned q, ph, u, p;
-      divmod((unsigned)s, (unsigned)a.decim, a.inv_decim, q, ph);
-      divmod(p0 + (unsigned)s, (unsigned)a.period, a.inv_period, u, p);
-      v2f* dst = Z + ph * a.ps + q;
-#pragma unroll 4
-      for (int c = 0; c < nc; ++c) {
-        unsigned m;
-        divmod(__umul24((unsigned)a.steps[c0 + c], p), (unsigned)a.period, a.inv_period, u, m);
-        const cf w = nco[m];
-        v2f z;
-        z.x = xr * w.re - xi * w.im;
-        z.y = xr * w.im + xi * w.re;
-        dst[c * chs] = z;
-      }
-    };
-    // pairs of samples on the grid of a pair's size (16 bytes of complex64); a pair that hangs
-    // over either end of the tile's samples is loaded singly
+    // every sample of the tile, mixed for the pass's channels.  Pairs of samples on the grid of a
+    // pair's size (16 bytes of complex64); a pair that hangs over either end is loaded singly
+    const MixStage<ChanArgs> mix{a, nco, Z, p0, c0, nc, chs};
     load_samples<F>(a.iq, row * a.row_stride + n0, cnt, a.scale, tid, kThreads, mix);
     __syncthreads();
 
@@ -159,39 +118,23 @@ int64_t channel_outputs(int64_t row_len, int64_t ntaps, int64_t decim) {
   return row_len < ntaps ? 0 : (row_len - ntaps) / decim + 1;
 }
 
-// Outputs per workgroup and channels per pass: the largest tile of 64, 32, 16, 8 at which all
-// channels fit the LDS; at 8 whatever fits (at least 8: a channel takes at most 960 entries)
-void channel_geometry(int ntaps, int decim, int channels, int& tile, int& cg) {
-  tile = kMaxTile;
-  while (tile > kMinTile && (int64_t)channels * channel_entries(tile, ntaps, decim) > kLdsSamples) tile >>= 1;
-  cg = kLdsSamples / channel_entries(tile, ntaps, decim);
-  if (cg > channels) cg = channels;
-}
-
 // Both entries: `format` is kIqCf32 for lora_channelize_batch, else a checked LORA_IQ_*
 int64_t channelize(const void* iq, int format, float scale, int64_t rows, int64_t row_len, int64_t row_stride,
                    int64_t first_sample, const float* taps, int64_t ntaps, int64_t decim, const float* nco,
                    int64_t period, const int32_t* steps, int64_t channels, float* out, int64_t out_stride,
                    int device, void* stream) {
-  if (!taps || !nco || !steps || !out) return set_last_error(LORA_EINVAL, "null taps / nco / steps / out");
-  if (rows < 0 || row_len < 0 || row_stride < 0 || out_stride < 0 || first_sample < 0)
-    return set_last_error(LORA_EINVAL, "negative rows / row_len / row_stride / out_stride / first_sample");
+  if (const char* bad = down_args_error(taps, nco, steps, out, rows, row_len, row_stride, out_stride, first_sample))
+    return set_last_error(LORA_EINVAL, bad);
   if (ntaps < 1 || ntaps > kMaxTaps) return set_last_error(LORA_EINVAL, "ntaps must be in 1..512");
   if (decim < 1 || decim > kMaxDecim) return set_last_error(LORA_EINVAL, "decim must be in 1..64");
-  if (period < 1 || period > kMaxPeriod) return set_last_error(LORA_EINVAL, "period must be in 1..4096");
-  if (channels < 1 || channels > kMaxChannels) return set_last_error(LORA_EINVAL, "channels must be in 1..32");
-  if (row_len >= (int64_t(1) << 31)) return set_last_error(LORA_EINVAL, "row_len must be < 2^31");
-  if (rows > 1 && row_stride < row_len) return set_last_error(LORA_EINVAL, "row_stride smaller than row_len");
+  if (const char* bad = down_shape_error(period, channels, rows, row_len, row_stride))
+    return set_last_error(LORA_EINVAL, bad);
   const int64_t W = channel_outputs(row_len, ntaps, decim);
-  if (out_stride < W) return set_last_error(LORA_EINVAL, "out_stride smaller than outputs per row");
   ChanArgs a{};
   channel_geometry((int)ntaps, (int)decim, (int)channels, a.tile, a.cg);
   a.W = W;
   a.gpr = (W + a.tile - 1) / a.tile;
-  // rows * gpr < 2^31, compared through the quotient so that nothing overflows
-  const int64_t lim = int64_t(1) << 31;
-  if (rows > 0 && a.gpr > 0 && (a.gpr >= lim || rows > (lim - 1) / a.gpr))
-    return set_last_error(LORA_EINVAL, "batch too large");
+  if (const char* bad = down_output_error(out_stride, W, rows, a.gpr)) return set_last_error(LORA_EINVAL, bad);
   if (rows == 0 || W == 0) return W;
   if (!iq) return set_last_error(LORA_EINVAL, "null iq");
   a.iq = iq;
@@ -211,25 +154,13 @@ int64_t channelize(const void* iq, int format, float scale, int64_t rows, int64_
   a.ps = a.tile + (a.ntaps - 1) / a.decim;
   a.inv_decim = 1.0f / (float)a.decim;
   a.inv_period = 1.0f / (float)a.period;
-  for (int c = 0; c < a.channels; ++c) {
-    const int64_t k = (int64_t)steps[c] % period;
-    a.steps[c] = (int)(k < 0 ? k + period : k);
-  }
+  bank_steps(steps, a.channels, period, a.steps);
   const size_t lds = (size_t)a.cg * channel_entries(a.tile, a.ntaps, a.decim) * sizeof(cf);
-  int prev = 0;
-  hipError_t e = hipGetDevice(&prev);
-  if (e == hipSuccess && prev != device) e = hipSetDevice(device);
-  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("channelize device: ") + hipGetErrorString(e));
   void (*const kernel)(ChanArgs) = format == LORA_IQ_CS16  ? k_channelize<LORA_IQ_CS16>
                                    : format == LORA_IQ_CS8 ? k_channelize<LORA_IQ_CS8>
                                    : format == LORA_IQ_CU8 ? k_channelize<LORA_IQ_CU8>
                                                            : k_channelize<kIqCf32>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(rows * a.gpr)), dim3(kThreads), lds, static_cast<hipStream_t>(stream),
-                     a);
-  e = hipGetLastError();
-  if (prev != device) hipSetDevice(prev);
-  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("k_channelize: ") + hipGetErrorString(e));
-  return W;
+  return launch_bank(kernel, "k_channelize", a, rows * a.gpr, kThreads, lds, device, stream, W);
 }
 
 }  // namespace

@@ -573,15 +573,11 @@ template <class K, class A>
 int64_t launch_frames(K kernel, const A& a, int64_t frames, int lg, int device, void* stream, int64_t ret) {
   const int64_t blocks = (frames + (kBlock >> lg) - 1) / (kBlock >> lg);
   if (blocks >= (int64_t(1) << 31)) return set_last_error(LORA_EINVAL, "batch too large");
-  int prev = 0;
-  hipError_t e = hipGetDevice(&prev);
-  if (e == hipSuccess && prev != device) e = hipSetDevice(device);
-  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("codec device: ") + hipGetErrorString(e));
+  lora::DeviceGuard guard(device);
+  if (guard.err != hipSuccess) return lora::hip_error("codec device", guard.err);
   hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), a);
-  e = hipGetLastError();
-  if (prev != device) hipSetDevice(prev);
-  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("codec launch: ") + hipGetErrorString(e));
-  return ret;
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? lora::hip_error("codec launch", e) : ret;
 }
 
 }  // namespace

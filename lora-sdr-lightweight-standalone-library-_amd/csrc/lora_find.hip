@@ -334,16 +334,12 @@ int64_t lora_find_frames_batch(const lora_find_params* p, const float* power, co
   const int sw1 = (sync & 15) << (p->sf - 4);
   a.dsync = (sw1 - a.sw0) & (a.N - 1);
   a.thresh = p->thresh_db;
-  int prev = 0;
-  hipError_t e = hipGetDevice(&prev);
-  if (e == hipSuccess && prev != p->device) e = hipSetDevice(p->device);
-  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("find device: ") + hipGetErrorString(e));
+  lora::DeviceGuard guard(p->device);
+  if (guard.err != hipSuccess) return lora::hip_error("find device", guard.err);
   hipLaunchKernelGGL(lora::k_find_frames, dim3((unsigned)rows), dim3(lora::kThreads), 0,
                      static_cast<hipStream_t>(stream), a);
-  e = hipGetLastError();
-  if (prev != p->device) hipSetDevice(prev);
-  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("k_find_frames: ") + hipGetErrorString(e));
-  return rows;
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? lora::hip_error("k_find_frames", e) : rows;
 }
 
 }  // extern "C"

@@ -112,6 +112,38 @@ void host_gen_chirp(std::complex<float>* out, int N, int osr, int NN, float f0, 
 // the C-ABI entry points of the other translation units.
 int set_last_error(int code, const std::string& msg);
 
+// LORA_EIO with the text "<step>: <HIP's text for e>".
+inline int hip_error(const char* step, hipError_t e) {
+  return set_last_error(LORA_EIO, std::string(step) + ": " + hipGetErrorString(e));
+}
+
+// `device` as the calling thread's current device for a scope, for every C entry that makes HIP
+// calls on a device of the caller's choosing.  The constructor reads the current device and
+// switches only if it differs; `err` is what that took (an entry returns hip_error("<entry>
+// device", g.err) unless it is hipSuccess).  The destructor switches back only if the constructor
+// switched, on every way out of the scope, and ignores a failure of that.  Lives on the stack: no
+// host allocation (tests/native/alloc_probe counts them per lora_demod_batch call).
+class DeviceGuard {
+ public:
+  explicit DeviceGuard(int device) {
+    err = hipGetDevice(&prev_);
+    if (err == hipSuccess && prev_ != device) {
+      err = hipSetDevice(device);
+      switched_ = err == hipSuccess;
+    }
+  }
+  ~DeviceGuard() {
+    if (switched_) (void)hipSetDevice(prev_);
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+  hipError_t err;
+
+ private:
+  int prev_ = 0;
+  bool switched_ = false;
+};
+
 // Fast symbol demodulator (lora_demod_fast.hip): register-blocked kissfft-exact FFT.
 // Returns false if the configuration is not covered (caller uses the generic kernel).
 bool launch_demod_fast(const KArgs& a, int s0, int64_t work, hipStream_t st);

@@ -37,15 +37,14 @@
 // k_channelize_resample is its complex64 instance, for lora_resample_channelize_batch, and
 // k_channelize_raw_resample<format> its cs16, cs8 and cu8 instances, for
 // lora_resample_channelize_raw_batch, whose integer samples become fp32 in the load in front of
-// the mixing.
+// the mixing.  The mix stage, the oscillator's arithmetic, the search for tile and cg and the
+// argument rules common to both down-converter banks are csrc/lora_bank.h's.
 #include <hip/hip_runtime.h>
 
 #include <string>
 
 #include "../../include/lora_mi355x.h"
-#include "lora_device.h"
-#include "lora_internal.h"
-#include "lora_iq_format.h"
+#include "lora_bank.h"
 
 #pragma clang fp contract(off)
 
@@ -53,10 +52,7 @@ namespace lora {
 namespace {
 
 constexpr int kMinWaves = 4, kMaxWaves = 8, kMaxThreads = 64 * kMaxWaves;
-constexpr int kMaxTile = 64, kMinTile = 8;
-constexpr int kLdsSamples = 8192;  // mixed samples a workgroup holds: 64 KiB
 constexpr int kMaxInterp = 16, kMaxDecim = 256, kMaxTaps = 4096, kMaxPhaseTaps = 512;
-constexpr int kMaxPeriod = 4096, kMaxChannels = 32;
 
 struct ResArgs {
   const void* iq;  // samples of the kernel's format
@@ -73,25 +69,6 @@ struct ResArgs {
   int j0[kMaxInterp], off[kMaxInterp], K[kMaxInterp];
   float scale;  // of an integer format's samples
 };
-
-__host__ __device__ constexpr int channel_entries(int tile, int reach, int decim) {
-  return decim * (tile + (reach - 1) / decim);
-}
-
-// a / d and a % d for 0 <= a < 2^24, d <= 4096 and a / d < 2^13, inv = 1.0f / d (the integer
-// bank's: the truncated product is off by at most one either way)
-__device__ __forceinline__ void divmod(unsigned a, unsigned d, float inv, unsigned& q, unsigned& r) {
-  q = (unsigned)((float)a * inv);
-  int rr = (int)a - (int)__umul24(q, d);
-  if (rr < 0) {
-    rr += (int)d;
-    --q;
-  } else if (rr >= (int)d) {
-    rr -= (int)d;
-    ++q;
-  }
-  r = (unsigned)rr;
-}
 
 template <int F>
 __device__ __forceinline__ void resample_tile(const ResArgs& a) {
@@ -120,25 +97,9 @@ __device__ __forceinline__ void resample_tile(const ResArgs& a) {
     const int nc = a.channels - c0 < a.cg ? a.channels - c0 : a.cg;
     if (c0) __syncthreads();  // the previous pass's FIR has read Z
 
-    // sample s of the tile, mixed for the pass's channels
-    auto mix = [&](int s, float xr, float xi) {
-      unsigned q, ph, u, p;
-      divmod((unsigned)s, (unsigned)a.decim, a.inv_decim, q, ph);
-      divmod(p0 + (unsigned)s, (unsigned)a.period, a.inv_period, u, p);
-      v2f* dst = Z + ph * a.ps + q;
-#pragma unroll 4
-      for (int c = 0; c < nc; ++c) {
-        unsigned m;
-        divmod(__umul24((unsigned)a.steps[c0 + c], p), (unsigned)a.period, a.inv_period, u, m);
-        const cf w = nco[m];
-        v2f z;
-        z.x = xr * w.re - xi * w.im;
-        z.y = xr * w.im + xi * w.re;
-        dst[c * chs] = z;
-      }
-    };
-    // pairs of samples on the grid of a pair's size (16 bytes of complex64); a pair that hangs
-    // over either end of the tile's samples is loaded singly
+    // every sample of the tile, mixed for the pass's channels.  Pairs of samples on the grid of a
+    // pair's size (16 bytes of complex64); a pair that hangs over either end is loaded singly
+    const MixStage<ResArgs> mix{a, nco, Z, p0, c0, nc, chs};
     load_samples<F>(a.iq, row * a.row_stride + n0, cnt, a.scale, tid, a.threads, mix);
     __syncthreads();
 
@@ -220,10 +181,7 @@ int residues(int ntaps, int interp, int decim, int* j0, int* off, int* K) {
 
 // u per workgroup, channels per pass and wavefronts per workgroup (the file header's rule)
 void resample_geometry(int reach, int interp, int decim, int channels, int& tile, int& cg, int& waves) {
-  tile = kMaxTile;
-  while (tile > kMinTile && (int64_t)channels * channel_entries(tile, reach, decim) > kLdsSamples) tile >>= 1;
-  cg = kLdsSamples / channel_entries(tile, reach, decim);
-  if (cg > channels) cg = channels;
+  channel_geometry(reach, decim, channels, tile, cg);
   const int group = 2 * (64 / tile), items = interp * ((cg + group - 1) / group);
   waves = kMinWaves;
   for (int w = kMinWaves + 1; w <= kMaxWaves; ++w)
@@ -235,21 +193,17 @@ int64_t resample_channelize(const void* iq, int format, float scale, int64_t row
                             int64_t row_stride, int64_t first_sample, const float* taps, int64_t ntaps,
                             int64_t interp, int64_t decim, const float* nco, int64_t period, const int32_t* steps,
                             int64_t channels, float* out, int64_t out_stride, int device, void* stream) {
-  if (!taps || !nco || !steps || !out) return set_last_error(LORA_EINVAL, "null taps / nco / steps / out");
-  if (rows < 0 || row_len < 0 || row_stride < 0 || out_stride < 0 || first_sample < 0)
-    return set_last_error(LORA_EINVAL, "negative rows / row_len / row_stride / out_stride / first_sample");
+  if (const char* bad = down_args_error(taps, nco, steps, out, rows, row_len, row_stride, out_stride, first_sample))
+    return set_last_error(LORA_EINVAL, bad);
   if (interp < 1 || interp > kMaxInterp) return set_last_error(LORA_EINVAL, "interp must be in 1..16");
   if (decim < 1 || decim > kMaxDecim) return set_last_error(LORA_EINVAL, "decim must be in 1..256");
   if (interp > decim) return set_last_error(LORA_EINVAL, "interp must not exceed decim: a rate-reducing bank only");
   if (ntaps < 1 || ntaps > kMaxTaps) return set_last_error(LORA_EINVAL, "ntaps must be in 1..4096");
   if ((ntaps + interp - 1) / interp > kMaxPhaseTaps)
     return set_last_error(LORA_EINVAL, "ceil(ntaps / interp) must be <= 512");
-  if (period < 1 || period > kMaxPeriod) return set_last_error(LORA_EINVAL, "period must be in 1..4096");
-  if (channels < 1 || channels > kMaxChannels) return set_last_error(LORA_EINVAL, "channels must be in 1..32");
-  if (row_len >= (int64_t(1) << 31)) return set_last_error(LORA_EINVAL, "row_len must be < 2^31");
-  if (rows > 1 && row_stride < row_len) return set_last_error(LORA_EINVAL, "row_stride smaller than row_len");
+  if (const char* bad = down_shape_error(period, channels, rows, row_len, row_stride))
+    return set_last_error(LORA_EINVAL, bad);
   const int64_t W = resample_outputs(row_len, ntaps, interp, decim);  // (row_len - 1) * interp < 2^35
-  if (out_stride < W) return set_last_error(LORA_EINVAL, "out_stride smaller than outputs per row");
   ResArgs a{};
   const int reach = residues((int)ntaps, (int)interp, (int)decim, a.j0, a.off, a.K);
   int waves = 0;
@@ -257,10 +211,7 @@ int64_t resample_channelize(const void* iq, int format, float scale, int64_t row
   a.threads = 64 * waves;
   a.W = W;
   a.gpr = ((W + interp - 1) / interp + a.tile - 1) / a.tile;
-  // rows * gpr < 2^31, compared through the quotient so that nothing overflows
-  const int64_t lim = int64_t(1) << 31;
-  if (rows > 0 && a.gpr > 0 && (a.gpr >= lim || rows > (lim - 1) / a.gpr))
-    return set_last_error(LORA_EINVAL, "batch too large");
+  if (const char* bad = down_output_error(out_stride, W, rows, a.gpr)) return set_last_error(LORA_EINVAL, bad);
   if (rows == 0 || W == 0) return W;
   if (!iq) return set_last_error(LORA_EINVAL, "null iq");
   a.iq = iq;
@@ -281,26 +232,13 @@ int64_t resample_channelize(const void* iq, int format, float scale, int64_t row
   a.ps = a.tile + (reach - 1) / a.decim;
   a.inv_decim = 1.0f / (float)a.decim;
   a.inv_period = 1.0f / (float)a.period;
-  for (int c = 0; c < a.channels; ++c) {
-    const int64_t k = (int64_t)steps[c] % period;
-    a.steps[c] = (int)(k < 0 ? k + period : k);
-  }
+  bank_steps(steps, a.channels, period, a.steps);
   const size_t lds = (size_t)a.cg * channel_entries(a.tile, reach, a.decim) * sizeof(cf);
-  int prev = 0;
-  hipError_t e = hipGetDevice(&prev);
-  if (e == hipSuccess && prev != device) e = hipSetDevice(device);
-  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("resample device: ") + hipGetErrorString(e));
   void (*const kernel)(ResArgs) = format == LORA_IQ_CS16  ? k_channelize_raw_resample<LORA_IQ_CS16>
                                   : format == LORA_IQ_CS8 ? k_channelize_raw_resample<LORA_IQ_CS8>
                                   : format == LORA_IQ_CU8 ? k_channelize_raw_resample<LORA_IQ_CU8>
                                                           : k_channelize_resample;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(rows * a.gpr)), dim3((unsigned)a.threads), lds,
-                     static_cast<hipStream_t>(stream), a);
-  e = hipGetLastError();
-  if (prev != device) hipSetDevice(prev);
-  if (e != hipSuccess)
-    return set_last_error(LORA_EIO, std::string("k_channelize_resample: ") + hipGetErrorString(e));
-  return W;
+  return launch_bank(kernel, "k_channelize_resample", a, rows * a.gpr, a.threads, lds, device, stream, W);
 }
 
 }  // namespace

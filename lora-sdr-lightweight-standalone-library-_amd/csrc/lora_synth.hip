@@ -16,7 +16,8 @@
 // passes of `cg` in channel order, the four sums of a lane staying in its registers across the
 // passes.  K is P or P - 1 for every phase, so the tap loop runs P - 1 uniform steps and one
 // predicated step.  The oscillator's position is found per output once, by the bank's 24-bit
-// multiply and reciprocal (no 64-bit modulo), and per channel the same way.
+// multiply and reciprocal (no 64-bit modulo), and per channel the same way (divmod; it, the
+// steps' reduction, the grid's limit and the launch are the banks' own: csrc/lora_bank.h).
 //
 // The kernel is a template over the output format (csrc/lora_iq_format.h): complex64, or cs16,
 // cs8, cu8 made by iq_store_code.  A tile's samples are put in LDS at the offset their global
@@ -28,9 +29,7 @@
 #include <string>
 
 #include "../../include/lora_mi355x.h"
-#include "lora_device.h"
-#include "lora_internal.h"
-#include "lora_iq_format.h"
+#include "lora_bank.h"
 
 #pragma clang fp contract(off)
 
@@ -40,7 +39,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kPerLane = 4;
 constexpr int kTile = kThreads * kPerLane;
-constexpr int kMaxTaps = 512, kMaxInterp = 64, kMaxPeriod = 4096, kMaxChannels = 32;
+constexpr int kMaxTaps = 512, kMaxInterp = 64;
 constexpr int kLdsBytes = 65536;
 
 struct SynthArgs {
@@ -64,21 +63,6 @@ __host__ __device__ constexpr int synth_pitch(int P, int interp) {
   return ((kTile - 1) / interp + 1 + P + 1) & ~1;
 }
 __host__ __device__ constexpr int out_buf_bytes(int format) { return kTile * iq_sample_bytes(format) + 16; }
-
-// a / d and a % d for 0 <= a < 2^24, d <= 4096 and a / d < 2^13, inv = 1.0f / d (the banks'
-// helper: the truncated product is off by at most one either way)
-__device__ __forceinline__ void divmod(unsigned a, unsigned d, float inv, unsigned& q, unsigned& r) {
-  q = (unsigned)((float)a * inv);
-  int rr = (int)a - (int)__umul24(q, d);
-  if (rr < 0) {
-    rr += (int)d;
-    --q;
-  } else if (rr >= (int)d) {
-    rr -= (int)d;
-    ++q;
-  }
-  r = (unsigned)rr;
-}
 
 template <int F>
 __global__ void __launch_bounds__(kThreads) k_synthesize(SynthArgs a) {
@@ -231,8 +215,7 @@ int64_t synthesize(const float* in, int64_t rows, int64_t chan_len, int64_t in_s
     return set_last_error(LORA_EINVAL, "negative rows / chan_len / in_stride / out_stride / first_sample");
   if (interp < 1 || interp > kMaxInterp) return set_last_error(LORA_EINVAL, "interp must be in 1..64");
   if (ntaps < 1 || ntaps > kMaxTaps) return set_last_error(LORA_EINVAL, "ntaps must be in 1..512");
-  if (period < 1 || period > kMaxPeriod) return set_last_error(LORA_EINVAL, "period must be in 1..4096");
-  if (channels < 1 || channels > kMaxChannels) return set_last_error(LORA_EINVAL, "channels must be in 1..32");
+  if (const char* bad = period_channels_error(period, channels)) return set_last_error(LORA_EINVAL, bad);
   if (chan_len >= (int64_t(1) << 31) || chan_len * interp >= (int64_t(1) << 31))
     return set_last_error(LORA_EINVAL, "chan_len * interp must be < 2^31");
   if (rows * channels > 1 && in_stride < chan_len)
@@ -244,9 +227,7 @@ int64_t synthesize(const float* in, int64_t rows, int64_t chan_len, int64_t in_s
   SynthArgs a{};
   a.W = W;
   a.gpr = (W + kTile - 1) / kTile;
-  // rows * gpr < 2^31, compared through the quotient so that nothing overflows
-  const int64_t lim = int64_t(1) << 31;
-  if (rows > 0 && a.gpr > 0 && rows > (lim - 1) / a.gpr) return set_last_error(LORA_EINVAL, "batch too large");
+  if (const char* bad = grid_error(rows, a.gpr)) return set_last_error(LORA_EINVAL, bad);
   if (rows == 0 || W == 0) return W;
   if (!in || !taps || !nco || !steps || !gains || !out)
     return set_last_error(LORA_EINVAL, "null in / taps / nco / steps / gains / out");
@@ -265,11 +246,8 @@ int64_t synthesize(const float* in, int64_t rows, int64_t chan_len, int64_t in_s
   a.inv_interp = 1.0f / (float)a.interp;
   a.inv_period = 1.0f / (float)a.period;
   a.inv_scale = inv_scale;
-  for (int c = 0; c < a.channels; ++c) {
-    const int64_t k = (int64_t)steps[c] % period;
-    a.steps[c] = (int)(k < 0 ? k + period : k);
-    a.gains[c] = gains[c];
-  }
+  bank_steps(steps, a.channels, period, a.steps);
+  for (int c = 0; c < a.channels; ++c) a.gains[c] = gains[c];
   // what the 64 KiB leave for samples after the taps and the tile's stored form: at least 4
   // channels per pass (a channel takes at most 1536 entries)
   a.pitch = synth_pitch(a.P, a.interp);
@@ -277,20 +255,11 @@ int64_t synthesize(const float* in, int64_t rows, int64_t chan_len, int64_t in_s
   a.cg = (kLdsBytes - fixed) / (a.pitch * (int)sizeof(cf));
   if (a.cg > a.channels) a.cg = a.channels;
   const size_t lds = (size_t)a.cg * a.pitch * sizeof(cf) + fixed;
-  int prev = 0;
-  hipError_t e = hipGetDevice(&prev);
-  if (e == hipSuccess && prev != device) e = hipSetDevice(device);
-  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("synthesize device: ") + hipGetErrorString(e));
   void (*const kernel)(SynthArgs) = format == LORA_IQ_CS16  ? k_synthesize<LORA_IQ_CS16>
                                     : format == LORA_IQ_CS8 ? k_synthesize<LORA_IQ_CS8>
                                     : format == LORA_IQ_CU8 ? k_synthesize<LORA_IQ_CU8>
                                                             : k_synthesize<kIqCf32>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(rows * a.gpr)), dim3(kThreads), lds, static_cast<hipStream_t>(stream),
-                     a);
-  e = hipGetLastError();
-  if (prev != device) hipSetDevice(prev);
-  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("k_synthesize: ") + hipGetErrorString(e));
-  return W;
+  return launch_bank(kernel, "k_synthesize", a, rows * a.gpr, kThreads, lds, device, stream, W);
 }
 
 }  // namespace

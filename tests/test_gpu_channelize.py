@@ -3,7 +3,7 @@ the numpy restatement of its definition (tests/channel_checker.py), compared as 
 patterns, and the wideband receive chain built on it against frames planted in a wideband
 signal.
 
-The kernel's tile (csrc/lora_channelize.hip, channel_geometry): a workgroup makes 64 outputs of
+The kernel's tile (csrc/lora_bank.h, channel_geometry): a workgroup makes 64 outputs of
 every channel where channels * decim * (64 + (ntaps-1) // decim) <= 8192 LDS entries, else 32,
 16 or 8; at 8 the channels are taken in passes of as many as fit.  The shapes below reach each
 of those paths."""

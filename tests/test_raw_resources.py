@@ -81,7 +81,7 @@ def static_lds_by_kernel(kernel_resources):
 def test_lds_fits_at_the_extremes(kernel_resources):
     """tests/test_resample_resources.py's sweep of the rational bank's limits, for each of its
     kernels; the integer bank's dynamic LDS is at most 8192 entries of 8 bytes by its geometry
-    rule (csrc/lora_channelize.hip, channel_geometry), so its kernels may keep no static LDS."""
+    rule (csrc/lora_bank.h, channel_geometry), so its kernels may keep no static LDS."""
     integer, rational = banks(kernel_resources)
     static = static_lds_by_kernel(kernel_resources)
     worst = 0
