@@ -497,6 +497,72 @@ int64_t lora_synthesize_raw_batch(const float* in, int64_t rows, int64_t chan_le
                                   int64_t channels, void* out, int format, float inv_scale, int64_t out_stride,
                                   int device, void* stream);
 
+/* Channel impairment: what stands between the synthesis bank and the down-converter banks.  Rows
+ * of complex64 in, the same rows out with a gain, a carrier offset and counter-based white
+ * Gaussian noise applied, from one kernel that reads each sample once and writes it once.  The
+ * reference's channel is three lines of host code in its AWGN test; this definition, like the
+ * banks', is the library's own.
+ *   in     `rows` rows of `row_len` complex samples, row r at in + 2*r*in_stride floats (device);
+ *          NULL: noise-only rows - gain and rotation are skipped and sigma is required;
+ *   first_sample, first_row (>= 0) the index of sample 0 in the recording and of row 0 among the
+ *          recording's rows;
+ *   seed   the noise generator's 64-bit key;
+ *   gain, fcw, phase, sigma  device arrays of `rows` entries, each of which may be NULL.  A NULL
+ *          array means that its stage's arithmetic is not performed at all (not performed with a
+ *          neutral value); fcw is the carrier offset as a 32-bit frequency control word, one step
+ *          fs / 2^32, phase the 32-bit starting phase, one step 2 pi / 2^32;
+ *   out    `rows` rows: output t of row r is sample r*out_stride + t of out (device).  out == in
+ *          is allowed, with equal strides.
+ * in and out need only be aligned to one sample.  For row r and output t let n = first_sample + t
+ * and R = first_row + r, both as 64-bit unsigned.  All float arithmetic is fp32, one rounding
+ * per operation, no contraction; K = 0x1.921fb6p-30f (fp32 pi times 2^-31); sincosf and logf are
+ * glibc's to the bit (|angle| <= pi everywhere), sqrtf is correctly rounded.
+ *   1. the gain (gain given):             xr = g*xr        xi = g*xi
+ *   2. the rotation (fcw or phase given, a missing one of the two counting as 0):
+ *        p = (uint32)phase[r] + (uint32)fcw[r] * (uint32)n          modulo 2^32
+ *        th = (float)(int32)p * K         (s, c) = sincosf(th)
+ *        yr = xr*c - xi*s                 yi = xr*s + xi*c
+ *      so the phase is continuous across chunks by construction;
+ *   3. the noise (sigma given): Philox4x32-10 with the standard multipliers 0xD2511F53,
+ *      0xCD9E8D57 and Weyl constants 0x9E3779B9, 0xBB67AE85, key (seed & 0xffffffff, seed >> 32),
+ *      counter (b lo, b hi, R lo, R hi) with b = n >> 1.  Sample n takes words (0, 1) of the
+ *      block when n is even and words (2, 3) when it is odd, as (w0, w1):
+ *        u = (float)(2*(w0 >> 9) + 1) * 0x1p-24f      exact, in (0, 1)
+ *        rad = sqrtf(-2.0f * logf(u))
+ *        ph = (float)(int32)w1 * K        (s, c) = sincosf(ph)
+ *        a = sigma*rad        nr = a*c        ni = a*s
+ *        yr = yr + nr         yi = yi + ni    (in == NULL: the output is (nr, ni) itself)
+ *      Each component is N(0, sigma^2) truncated at 5.77 sigma.  For a signal of amplitude A an
+ *      SNR of snr dB is sigma = A * 10^(-snr/20) / sqrt(2);
+ *   4. the store: complex64, or with lora_impair_raw_batch - `void* out, int format, float
+ *      inv_scale` in place of `float* out` - cs16, cs8 or cu8 codes by exactly
+ *      lora_synthesize_raw_batch's rule (v = y*inv_scale, + 127.5f for cu8, clamp(rintf(v)), a
+ *      NaN stores the format's zero); out_stride stays in samples.
+ * Infinities and NaN in `in` propagate as this arithmetic makes them, with
+ * lora_channelize_batch's caveat about a NaN's sign and payload.
+ * A sample's value depends on (seed, R, n) and its row's parameters alone - not on chunking,
+ * row count, alignment or which lane computed it: one call over a row equals, bit for bit, any
+ * split of it into calls with first_sample advanced, and likewise for rows and first_row.
+ * Not covered: a fractional delay, multipath, frequency drift, and DC offset, IQ imbalance or any
+ * other front-end effect.  An integer delay is the caller's slice.
+ *
+ * Both entries enqueue one kernel on `stream` of `device`, allocate and synchronise nothing,
+ * need no workspace and write samples 0 .. row_len-1 of every row and nothing else.  rows == 0
+ * or row_len == 0: no launch.  LORA_EINVAL, before any HIP call, first rule first: negative
+ * sizes, first_sample or first_row; row_len >= 2^31; with more than one row an in_stride (in
+ * given) or out_stride smaller than row_len; out == in with unequal strides; an in or out that
+ * is not aligned to one sample; a `format` that is none of the three (0 included); a grid beyond
+ * 2^31 (rows * ceil(row_len / 1024)); and with work to do a NULL out, in == NULL with sigma ==
+ * NULL, or nothing to do at all (all four arrays NULL).  Returns row_len. */
+int64_t lora_impair_batch(const float* in, int64_t rows, int64_t row_len, int64_t in_stride, int64_t first_sample,
+                          int64_t first_row, uint64_t seed, const float* gain, const int32_t* fcw,
+                          const int32_t* phase, const float* sigma, float* out, int64_t out_stride, int device,
+                          void* stream);
+int64_t lora_impair_raw_batch(const float* in, int64_t rows, int64_t row_len, int64_t in_stride,
+                              int64_t first_sample, int64_t first_row, uint64_t seed, const float* gain,
+                              const int32_t* fcw, const int32_t* phase, const float* sigma, void* out, int format,
+                              float inv_scale, int64_t out_stride, int device, void* stream);
+
 /* lora_modulate for `frames` independent frames: symbols [frames][sym_count] ->
  * iq [frames][(sym_count+2)*N*osr] (2 sync up-chirps then one chirp per symbol,
  * phase-continuous within a frame, LoRaMod.cpp:8-41).  Returns samples per frame. */

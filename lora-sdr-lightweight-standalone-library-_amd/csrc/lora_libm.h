@@ -546,6 +546,39 @@ LM_FN float lm_logf(float x) {
   return (float)y;
 }
 
+// K-way lockstep lm_logf for positive normal finite x other than 1.0f (identical arithmetic per
+// element: the branches lm_logf takes for 1, zero, subnormals, negatives, inf and NaN are the
+// only thing left out), the element chains written interleaved as in lm_sincosf_fast_k.
+template <int K>
+LM_FN void lm_logf_pos_k(const float* x, float* out) {
+  const double Ln2 = 0x1.62e42fefa39efp-1;
+  const double A0 = lm_asdouble(0xbfd00ea348b88334ull);
+  const double A1 = lm_asdouble(0x3fd5575b0be00b6aull);
+  const double A2 = lm_asdouble(0xbfdffffef20a4123ull);
+  double r[K], y0[K], r2[K], y[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const uint32_t ix = lm_asuint(x[k]);
+    const uint32_t tmp = ix - 0x3f330000u;
+    const int i = (int)((tmp >> (23 - 4)) % 16);
+    const int e = (int32_t)tmp >> 23;
+    const uint32_t iz = ix - (tmp & (0x1ffu << 23));
+    double invc, logc;
+    lm_logf_tab(i, &invc, &logc);
+    r[k] = lm_fma((double)lm_asfloat(iz), invc, -1.0);
+    y0[k] = lm_fma((double)e, Ln2, logc);
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    r2[k] = r[k] * r[k];
+    y[k] = lm_fma(A1, r[k], A2);
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) y[k] = lm_fma(A0, r2[k], y[k]);
+#pragma unroll
+  for (int k = 0; k < K; ++k) out[k] = (float)lm_fma(y[k], r2[k], y0[k] + r[k]);
+}
+
 LM_FN float lm_log10f(float x) {
   const float two25 = 33554432.0f;
   const float ivln10 = lm_asfloat(0x3ede5bd9u);

@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = (
     "lora_synthesize_outputs",
     "lora_synthesize_batch",
     "lora_synthesize_raw_batch",
+    "lora_impair_batch",
+    "lora_impair_raw_batch",
     "lora_mod_batch",
     "lora_estimate_offsets_batch",
     "lora_compensate_offsets_batch",
@@ -214,6 +216,15 @@ def lib() -> C.CDLL:
     L.lora_synthesize_raw_batch.restype = C.c_int64
     L.lora_synthesize_raw_batch.argtypes = (L.lora_synthesize_batch.argtypes[:14] + [C.c_int, C.c_float] +
                                             L.lora_synthesize_batch.argtypes[14:])
+    # the channel impairment stage (csrc/lora_impair.hip): gain, fcw, phase and sigma are device
+    # arrays (any may be NULL); the raw entry has (out, format, inv_scale) in place of out
+    L.lora_impair_batch.restype = C.c_int64
+    L.lora_impair_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                    C.c_void_p]
+    L.lora_impair_raw_batch.restype = C.c_int64
+    L.lora_impair_raw_batch.argtypes = (L.lora_impair_batch.argtypes[:12] + [C.c_int, C.c_float] +
+                                        L.lora_impair_batch.argtypes[12:])
     L.lora_mod_batch.restype = C.c_int64
     L.lora_mod_batch.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_float, C.c_uint8, C.c_void_p,
                                  C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]

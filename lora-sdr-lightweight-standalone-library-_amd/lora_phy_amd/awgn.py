@@ -21,6 +21,14 @@ Two harnesses, both host-driven with one batched GPU call per SNR point:
     symbol CFO/timing estimate + per-symbol CFO rotation (the reference's "preamble
     detect + CFO correct", LoRaDemod.cpp:79-157) -> ``lora_decode``.  Reports SER, BER,
     PER and returns the noisy IQ so callers can check the GPU against the oracle.
+
+``sweep_receive(sf, snr_dbs, frames, frame_symbols, ...)``
+    Detection probability of the stream receiver, everything on the device: GPU-modulated
+    frames planted at known starts in zero rows -> ``stream.impair`` in place of a copy (counter-
+    based AWGN and an optional carrier offset, reproducible on the CPU) -> ``stream.receive_device``
+    -> counts of the planted starts returned exactly, of the returned starts that were not
+    planted and of the detected frames whose symbols all equal the planted ones.  Noise-only
+    batches give false starts per window.  One synchronisation, at the end, for the counts.
 """
 from __future__ import annotations
 
@@ -184,4 +192,95 @@ def sweep_chain(sf: int, snr_dbs: Sequence[float], frames: int = 1000, payload_l
             rec["iq"] = iq
             rec["result"] = res
         out.append(rec)
+    return out
+
+
+# --------------------------------------------------------------------------------------
+# The stream receiver's detection probability (stream.impair -> stream.receive_device)
+# --------------------------------------------------------------------------------------
+
+def sweep_receive(sf: int, snr_dbs: Sequence[float], frames: int = 2000, frame_symbols: int = 16, osr: int = 1,
+                  hop: Optional[int] = None, thresh_db: float = 0.0, cfo_bins: float = 0.0, seed: int = 1234,
+                  frames_per_row: int = 4, noise_windows: int = 0, noise_batch_samples: int = 1 << 27,
+                  sync: int = 0x12, device=None) -> List[Dict]:
+    """Detection probability and false starts of ``stream.receive_device`` under ``stream.impair``.
+
+    Layout: ``ceil(frames / frames_per_row)`` zero rows, each with ``frames_per_row`` frames of
+    ``frame_symbols`` random data symbols (GPU ``modulate``, amplitude 1) at starts that are
+    multiples of ``osr``, every frame after a gap drawn uniformly from 0 .. 2 * step - 1 chips (and
+    one such gap behind the last).  The layout and the symbols are drawn once from ``seed`` and
+    serve every SNR point; the noise of point i is ``impair``'s with this ``seed`` and ``first_row
+    = i * rows``, so no two points share a noise sample.  ``cfo_bins`` is the carrier offset in
+    FFT bins (``cfo_bins / (N * osr)`` cycles per sample).  ``hop`` defaults to ``step // 4``.
+
+    Per SNR point one record: ``planted``, ``detected`` (planted starts returned exactly),
+    ``false_starts`` (returned starts that were not planted), ``all_symbols_correct`` (detected
+    frames whose ``frame_symbols`` symbols all equal the planted ones), ``windows`` (scanned) and
+    the rates ``p_detect``, ``p_all_correct_given_detected``.  With ``noise_windows > 0`` a last
+    record (``"noise_only": True``) has the false starts over at least that many windows of noise
+    alone (``impair(None, ...)`` in batches of about ``noise_batch_samples``).  Everything runs on
+    the device; the counts of all points come to the host in one copy at the end."""
+    from . import stream
+
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    N = 1 << sf
+    step = N * osr
+    hop = step // 4 if hop is None else int(hop)
+    S, K = int(frame_symbols), int(frames_per_row)
+    frame_len = (S + 2) * step
+    R = -(-int(frames) // K)
+    F = R * K
+    rng = np.random.default_rng(seed)
+    gaps = rng.integers(0, 2 * N, (R, K + 1)) * osr
+    starts = np.cumsum(gaps[:, :K], axis=1) + np.arange(K) * frame_len          # [R, K]
+    L = int((starts[:, -1] + frame_len + gaps[:, K]).max())
+    syms = rng.integers(0, N, (F, S)).astype(np.int32)
+    plan = DemodPlan(sf, osr, 125000, "none", dechirp=True, mode="legacy", device=dev)
+    starts_t = torch.from_numpy(starts).to(dev)
+    syms_t = torch.from_numpy(syms).to(dev).view(R, K, S)
+    clean = torch.zeros((R, L), dtype=torch.complex64, device=dev)
+    at = (torch.arange(R, device=dev)[:, None] * L + starts_t).reshape(-1)
+    clean.view(-1)[at[:, None] + torch.arange(frame_len, device=dev)] = modulate(
+        torch.from_numpy(syms).to(dev), sf, osr, 125000, 1.0, sync)
+    work = torch.empty_like(clean)
+    W = (L - step) // hop + 1
+    cfo = float(cfo_bins) / step
+    counts = []
+    for i, snr in enumerate(snr_dbs):
+        stream.impair(clean, snr_db=float(snr), cfo=cfo if cfo_bins else None, seed=seed, first_row=i * R, out=work)
+        got = stream.receive_device(plan, work, S, hop, sync, thresh_db)
+        valid = got.found.valid                                                  # [R, cap]
+        same = got.found.starts[:, :, None] == starts_t[:, None, :]              # [R, cap, K]
+        hit = same.any(2) & valid
+        which = same.to(torch.int8).argmax(2)                                    # the planted frame of a hit
+        want = torch.gather(syms_t, 1, which[:, :, None].expand(-1, -1, S))
+        rx = got.result.symbols.to(torch.int32).view(R, -1, S) % N
+        right = hit & (rx == want).all(2)
+        counts.append(torch.stack([hit.sum(), (valid & ~hit).sum(), right.sum(),
+                                   (got.found.count.to(torch.int64) - valid.sum(1)).sum()]))
+    noise_counts, noise_total = [], 0
+    if noise_windows > 0:
+        Ln = max(frame_len + step, min(int(noise_batch_samples), 1 << 24))
+        Rn = max(1, int(noise_batch_samples) // Ln)
+        Wn = (Ln - step) // hop + 1
+        buf = torch.empty((Rn, Ln), dtype=torch.complex64, device=dev)
+        b = 0
+        while noise_total < noise_windows:
+            stream.impair(None, sigma=1.0, seed=seed + 1, first_row=b * Rn, out=buf, rows=Rn, length=Ln, device=dev)
+            noise_counts.append(stream.receive_device(plan, buf, S, hop, sync, thresh_db).found.count.sum())
+            noise_total += Rn * Wn
+            b += 1
+    got = torch.stack(counts).cpu().numpy() if counts else np.zeros((0, 4), np.int64)  # the synchronisation
+    out = []
+    for snr, (hit, false, right, dropped) in zip(snr_dbs, got.tolist()):
+        out.append({"sf": sf, "osr": osr, "snr_db": float(snr), "cfo_bins": float(cfo_bins), "hop": hop,
+                    "thresh_db": float(thresh_db), "frame_symbols": S, "planted": F, "detected": hit,
+                    "false_starts": false, "all_symbols_correct": right, "not_stored": dropped,
+                    "windows": R * W, "p_detect": hit / F,
+                    "p_all_correct_given_detected": (right / hit) if hit else None})
+    if noise_counts:
+        false = int(torch.stack(noise_counts).sum().cpu())
+        out.append({"sf": sf, "osr": osr, "noise_only": True, "hop": hop, "thresh_db": float(thresh_db),
+                    "frame_symbols": S, "windows": noise_total, "false_starts": false,
+                    "false_starts_per_million_windows": false * 1e6 / noise_total})
     return out

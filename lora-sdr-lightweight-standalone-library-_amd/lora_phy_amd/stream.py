@@ -29,8 +29,18 @@ It is defined on the detector's outputs alone:
 Limits.  The resolution is ``osr`` samples: the demodulator's own osr-phase estimate takes it
 from there.  A stream that begins inside a frame can produce a false start, with probability
 of about 1/N per pair of consecutive symbols; a sync word with equal nibbles makes any repeated
-symbol a candidate.  No detection-probability figure is claimed, because none has been
-measured.  A perfectly aligned noiseless window has no noise floor (``power_avg = -inf``, so
+symbol a candidate.  Detection probability, measured once (profiles/stream/detect_prob.json,
+``tools/detect_prob.py``: osr 1, frames of 16 symbols at unit amplitude under ``impair``'s noise,
+``hop = step / 4``, ``thresh_db = 0``, 2,000 frames per point, a detection being a planted start
+returned exactly): the finder's edge lies between 0 and +5 dB at every SF - SF7 0.06 / 0.66 / 0.995
+at 0 / +2 / +4 dB, SF12 0.007 / 0.77 / 1.0 at 0 / +2 / +3 dB, nothing at or below -2 dB - because
+``power - power_avg`` is the peak bin over the sum of all the others, which follows the SNR per
+sample: with the default threshold the finder does not use the spreading gain, though every
+detected frame demodulated with all its symbols right.  A carrier offset of a quarter bin costs
+about 2 dB more (SF7 0.82, SF12 0.95 at +5 dB): it moves the refinement's peak between bins.
+Noise alone gave no false start in 10^7 windows per SF; with frames present up to 150 returned
+starts per 10^6 windows were not the planted ones (SF7, +1 dB).  Other thresholds, osr > 1 and
+integer-bin offsets have not been measured.  A perfectly aligned noiseless window has no noise floor (``power_avg = -inf``, so
 ``snr = +inf`` and it passes any threshold); a silent window gives NaN and never passes.
 
 The finder on the device.  ``find_frames`` computes the candidates on the device, copies every
@@ -51,7 +61,8 @@ rows at once.  Channel centres are multiples of ``fs / period``; the input rate 
 ``bw * osr * decim / interp`` - an integer ``decim`` alone, or with ``interp > 1`` the rational
 bank (lora_resample_channelize_batch), whose ratios are those with ``interp <= 16`` and ``decim <=
 256`` (2.4 MS/s to 125 kS/s is 5/96; 2.048 MS/s, 125/2048, is beyond them); the finder's 125 kHz
-restriction is inherited; and again no detection-probability figure is claimed.
+restriction is inherited; and the detection probability above was measured on narrowband rows,
+not through a bank.
 
 Raw SDR samples.  No radio delivers complex64: an RTL-SDR writes unsigned 8-bit pairs (cu8), a
 HackRF signed 8-bit pairs (cs8), USRP, Pluto, LimeSDR and most ``.sigmf-data`` files signed 16-bit
@@ -91,7 +102,8 @@ from .demod import DemodPlan, DemodResult, DetectMetrics, _check_iq, _require_cu
 
 __all__ = ["find_frames", "extract_frames", "receive", "lowpass_taps", "nco_table", "Channelizer",
            "receive_wideband", "raw_scale", "raw_to_complex", "Synthesizer", "transmit_wideband",
-           "FoundFrames", "StreamFrames", "find_frames_device", "receive_device", "receive_wideband_device"]
+           "FoundFrames", "StreamFrames", "find_frames_device", "receive_device", "receive_wideband_device",
+           "impair", "cfo_word", "noise_sigma"]
 
 _NONE = -(1 << 62)  # "no candidate here" in the packed starts
 
@@ -913,3 +925,161 @@ def transmit_wideband(synth: Synthesizer, frames: torch.Tensor, channel, starts,
         idx = base[:, None] + torch.arange(frame_len, device=synth.device)
         chans.view(-1)[idx] = frames
     return synth.run(chans, first_sample, out, dtype, inv_scale)
+
+
+def cfo_word(cycles_per_sample: float) -> int:
+    """A carrier offset in cycles per sample as ``impair``'s 32-bit frequency control word:
+    ``round(cycles_per_sample * 2**32)`` to nearest, wrapped into int32 (one step is fs / 2**32;
+    0.5 and -0.5 cycles per sample are the same word, -2**31)."""
+    w = int(round(float(cycles_per_sample) * 4294967296.0)) & 0xFFFFFFFF
+    return w - (1 << 32) if w >= 1 << 31 else w
+
+
+def noise_sigma(snr_db: float, amplitude: float = 1.0) -> float:
+    """The per-component noise deviation that puts a signal of ``amplitude`` at ``snr_db`` dB:
+    ``amplitude * 10**(-snr_db / 20) / sqrt(2)`` (``awgn.sweep_chain``'s convention: the complex
+    noise power is ``2 * sigma**2``)."""
+    return float(amplitude) * 10.0 ** (-float(snr_db) / 20.0) / float(np.sqrt(2.0))
+
+
+def _row_values(v, R: int, dev: torch.device, name: str, words: bool) -> Optional[torch.Tensor]:
+    """A per-row parameter as the kernel takes it: None, or a contiguous [R] tensor on ``dev`` -
+    float32, or int32 words when ``words`` (a float value is in cycles and becomes
+    ``round(v * 2**32)`` wrapped into int32, an int32 tensor is taken as words).  Tensor
+    arithmetic only: nothing is read back."""
+    if v is None:
+        return None
+    if isinstance(v, torch.Tensor):
+        if v.dim() > 1 or (v.dim() == 1 and v.shape[0] not in (1, R)):
+            raise ValueError(f"{name} must be a scalar or one value per row ([{R}])")
+        if v.device != dev:
+            raise ValueError(f"{name} is on {v.device}, the samples are on {dev}")
+        t = v.reshape(-1).expand(R) if v.numel() == 1 else v
+        if words and t.dtype == torch.int32:
+            return t.contiguous()
+        if not words:
+            return t.to(torch.float32).contiguous()
+        w = torch.round(t.to(torch.float64) * 4294967296.0).to(torch.int64) & 0xFFFFFFFF
+        return torch.where(w >= 1 << 31, w - (1 << 32), w).to(torch.int32).contiguous()
+    if words:
+        return torch.full((R,), cfo_word(v), dtype=torch.int32, device=dev)
+    return torch.full((R,), float(np.float32(v)), dtype=torch.float32, device=dev)
+
+
+def impair(iq: Optional[torch.Tensor], *, sigma=None, snr_db=None, amplitude=1.0, cfo=None, phase=None, gain=None,
+           seed: int = 0, first_sample: int = 0, first_row: int = 0, out: Optional[torch.Tensor] = None, dtype=None,
+           scale: Optional[float] = None, rows: Optional[int] = None, length: Optional[int] = None,
+           device=None) -> torch.Tensor:
+    """The channel between a transmitter and a receiver, one kernel that reads the samples once and
+    writes them once (lora_impair_batch, lora_impair_raw_batch; the exact arithmetic is in
+    include/lora_mi355x.h and is this project's own): per row a ``gain``, a carrier offset ``cfo``
+    in cycles per sample with a starting ``phase`` in cycles (both through ``cfo_word``: a 32-bit
+    phase accumulator, continuous across chunks by construction), and white Gaussian noise of
+    deviation ``sigma`` per component - or ``snr_db`` for a signal of ``amplitude``
+    (``noise_sigma``); the two are mutually exclusive.  Each is a scalar or a per-row tensor on
+    the samples' device (an int32 tensor for ``cfo`` or ``phase`` is taken as words), and a stage
+    whose parameter is None is not performed at all.
+
+    ``iq``: [L] or [R, L] complex64 CUDA samples (unit sample stride, rows that do not overlap;
+    any slice will do, the kernel needs no alignment beyond one sample), or None for noise-only
+    rows of ``rows`` x ``length`` (``rows=None``: one [length] row) on ``device``.  The noise of
+    sample t of row r is a function of ``(seed, first_row + r, first_sample + t)`` alone (Philox
+    4x32-10 and Box-Muller, each component N(0, sigma^2) truncated at 5.77 sigma), so a
+    recording impaired in chunks, or by several ranks a few rows each, is bit for bit the
+    recording impaired at once, and a host restatement reproduces every bit.
+
+    ``out``: a tensor to write into, of the result's shape and dtype; ``out=iq`` runs in place.
+    ``dtype`` ``torch.int16``, ``torch.int8`` or ``torch.uint8`` gives raw samples [.., L, 2]
+    stored by ``Synthesizer.run``'s rule, ``scale`` being its ``inv_scale`` (default 32768, 128,
+    127.5; ``scale`` without ``dtype`` is a ``ValueError``).  Returns the result.  One kernel on
+    the current stream; it never synchronises and never reads device memory on the host.
+
+    Not covered: a fractional delay, multipath, frequency drift, and DC offset, IQ imbalance or
+    any other front-end effect; an integer delay is a slice."""
+    if sigma is not None and snr_db is not None:
+        raise ValueError("sigma and snr_db are mutually exclusive")
+    if dtype is None:
+        if scale is not None:
+            raise ValueError("scale belongs to a raw integer dtype; a complex64 output has none")
+        odt = torch.complex64
+    else:
+        if dtype not in _INV_SCALE:
+            raise TypeError(f"raw samples are int16 (cs16), int8 (cs8) or uint8 (cu8), not {dtype}")
+        odt = dtype
+        scale = float(np.float32(_INV_SCALE[dtype] if scale is None else scale))
+    raw = dtype is not None
+    if iq is None:
+        if length is None:
+            raise ValueError("noise-only rows (iq=None) need length, and rows for more than one")
+        one = rows is None
+        R, L = (1 if one else int(rows)), int(length)
+        if R < 0 or L < 0:
+            raise ValueError("rows and length must be >= 0")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise TypeError("impair runs on a CUDA (HIP) device; there is no CPU fallback")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if sigma is None and snr_db is None:
+            raise ValueError("noise-only rows need sigma or snr_db")
+        if cfo is not None or phase is not None or gain is not None:
+            raise ValueError("noise-only rows take no cfo, phase or gain")
+        in_ptr, in_stride = None, L
+    else:
+        if rows is not None or length is not None or device is not None:
+            raise ValueError("rows, length and device belong to noise-only rows (iq=None)")
+        _require_cuda(iq, "iq")
+        one = iq.dim() == 1
+        dev = iq.device
+        x = _check_iq(iq, dev)
+        R, L = x.shape
+        in_ptr, in_stride = x.data_ptr(), (x.stride(0) if R > 1 else L)
+    first_sample, first_row, seed = int(first_sample), int(first_row), int(seed)
+    if first_sample < 0 or first_row < 0:
+        raise ValueError("first_sample and first_row must be >= 0")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be in 0 .. 2**64 - 1")
+    if snr_db is not None:
+        if isinstance(snr_db, torch.Tensor) or isinstance(amplitude, torch.Tensor):
+            db = snr_db if isinstance(snr_db, torch.Tensor) else torch.tensor(float(snr_db), device=dev)
+            sigma = amplitude * torch.pow(10.0, -db.to(torch.float64) / 20.0) / float(np.sqrt(2.0))
+        else:
+            sigma = noise_sigma(snr_db, amplitude)
+    g_t = _row_values(gain, R, dev, "gain", False)
+    s_t = _row_values(sigma, R, dev, "sigma", False)
+    f_t = _row_values(cfo, R, dev, "cfo", True)
+    p_t = _row_values(phase, R, dev, "phase", True)
+    if g_t is None and s_t is None and f_t is None and p_t is None:
+        raise ValueError("nothing to do: give at least one of sigma / snr_db, cfo, phase, gain")
+    lead = () if one else (R,)
+    tail = (2,) if raw else ()
+    per = 2 if raw else 1  # elements per sample
+    if out is None:
+        out = torch.empty(lead + (L,) + tail, dtype=odt, device=dev)
+    else:
+        _require_cuda(out, "out")
+        if out.dtype != odt:
+            raise TypeError(f"out must be {odt}")
+        ok = out.device == dev and tuple(out.shape) == lead + (L,) + tail and (not raw or out.stride(-1) == 1)
+        if ok and L > 1:
+            ok = out.stride(len(lead)) == per
+        if ok and R > 1 and not one:
+            ok = out.stride(0) % per == 0 and out.stride(0) >= per * L
+        if not ok:
+            raise ValueError(f"out must be a {odt} {list(lead + (L,) + tail)} tensor on {dev} with unit stride "
+                             "within a row and rows that do not overlap")
+    if R == 0 or L == 0:
+        return out  # nothing to launch (and an empty tensor has no address to pass)
+    out_stride = (out.stride(0) // per) if (not one and R > 1) else L
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    head = (in_ptr, R, L, in_stride, first_sample, first_row, seed, ptr(g_t), ptr(f_t), ptr(p_t), ptr(s_t),
+            out.data_ptr())
+    tail_args = (out_stride, dev.index, _stream_handle(dev))
+    lib = _capi.lib()
+    if raw:
+        got = lib.lora_impair_raw_batch(*head, _RAW[dtype][0], scale, *tail_args)
+    else:
+        got = lib.lora_impair_batch(*head, *tail_args)
+    got = _capi.check(got)
+    assert got == L, (got, L)
+    return out
