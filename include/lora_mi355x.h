@@ -296,6 +296,38 @@ int64_t lora_find_frames_batch(const lora_find_params* params, const float* powe
                                const int64_t* first, int64_t row_len, int64_t capacity, int64_t* starts,
                                int32_t* count, int64_t* end, void* stream);
 
+/* The finder for frames that state their own length ("Self-describing frames", below): the
+ * candidates are listed, a caller decodes the header at each (lora_gather_frames_batch,
+ * lora_demod_batch, lora_decode_frame_batch in header-only mode), and the greedy pass runs over
+ * the slots whose header is good, each frame as long as its header says.  Like the finder above
+ * the rule is the library's own.
+ *
+ * lora_find_candidates_batch: the candidate rule and the refinement of lora_find_frames_batch,
+ * unchanged (same inputs, same fp32 comparison; params.frame_symbols is not used).  Per row, in
+ * increasing w, a candidate's start is listed when start >= 0 and start + 10 * step <= row_len
+ * (the two sync symbols and the header's eight fit), unless it equals the row's last listed
+ * start.  count[r] = the starts listed (may exceed capacity), starts [rows][capacity] = the first
+ * min(count, capacity) of them, then -1.
+ * lora_select_frames_batch: per row, `slots` candidate slots - cand_starts, and status and nsym
+ * as lora_decode_frame_batch gave them for each, all [rows][slots].  In slot order, slot j is
+ * accepted when status is LORA_FRAME_OK, nsym <= max_symbols, start >= first (and >= 0: an
+ * empty slot is -1) and start + (2 + nsym) * step <= row_len; first then becomes that end.
+ * (The fixed-length pass's jump to first - step/2 needs no restating: |d * osr| <= step/2.)
+ * count, starts and end as lora_find_frames_batch's, and nsym [rows][capacity], 0 in the empty
+ * slots.  `first`: one int64 per row on the device, or NULL for 0.
+ * Both: one kernel on `stream`, one workgroup per row, nothing allocated or synchronised, every
+ * output fully written (also with no window to test, no slot, or capacity 0); rows == 0: no
+ * launch.  LORA_EINVAL before any HIP call as for lora_find_frames_batch, and for step < 1,
+ * max_symbols < 0 or slots >= 2^31.  Return rows. */
+int64_t lora_find_candidates_batch(const lora_find_params* params, const float* power, const float* power_avg,
+                                   const uint16_t* index, int64_t rows, int64_t W, int64_t stride,
+                                   int64_t row_len, int64_t capacity, int64_t* starts, int32_t* count,
+                                   void* stream);
+int64_t lora_select_frames_batch(const int64_t* cand_starts, const int32_t* status, const int32_t* nsym,
+                                 int64_t rows, int64_t slots, const int64_t* first, int64_t row_len, int64_t step,
+                                 int64_t max_symbols, int64_t capacity, int64_t* starts, int32_t* out_nsym,
+                                 int32_t* count, int64_t* end, int device, void* stream);
+
 /* Digital down-converter bank: one wideband stream in, `channels` streams at the demodulator's
  * rate out, from one read of the wideband data.  The reference has no channelizer; this
  * definition is the library's own (like the finder's rule and the soft bits).
@@ -651,6 +683,90 @@ int64_t lora_encode_chain_batch(int sf, int rdd, const uint8_t* payload, int64_t
  * (the block count of diagonalInterleaveSx, LoRaCodes.hpp:376-394).  Host arithmetic only, no
  * HIP call. */
 int64_t lora_chain_symbols(int sf, int rdd, int64_t nbytes);
+
+/* ---- Self-describing frames: an explicit header in front of the coding chain ---------------
+ * A frame that states its own payload length, coding rate and CRC flag, so that a receiver
+ * needs no frame length from its caller.  The reference has the two primitives an explicit
+ * header exists for (headerChecksum, LoRaCodes.hpp:43-67; sx1272DataChecksum, LoRaCodes.hpp:
+ * 92-105) but no header: the layout is this library's own, in the familiar LoRa arrangement (a
+ * first block at rate 4/8 on sf - 2 bits per symbol, 5 header nibbles, a payload CRC16).  No
+ * on-air interoperability is claimed; as in the reference there is no preamble or SFD.
+ *
+ * For sf in 7..12, rdd in 0..4, n in 0..255 payload bytes P and crc in {0, 1}:
+ *   data bytes  D = P, then with crc the two bytes c & 0xFF, c >> 8, c = sx1272DataChecksum of
+ *               all n bytes of P; data nibbles high first, ND = 2 * (n + 2 * crc) of them
+ *   header      h0 = n, h1 = rdd << 1 | crc, h2 = headerChecksum({h0, h1}) (5 bits); nibbles
+ *               h0 >> 4, h0 & 15, h1 & 15, h2 >> 4, h2 & 15
+ *   block 0     sf - 2 codewords: Hamming 8/4 (LoRaCodes.hpp:229-242) of the five header
+ *               nibbles, then of the first sf - 7 data nibbles (a zero codeword where the data
+ *               has run out); codewords 5 onward are whitened (Sx1272ComputeWhiteningLfsr on
+ *               them with bit offset 0 and rdd 4, LoRaCodes.hpp:176-189), the header's are not;
+ *               diagonalInterleaveSx at PPM sf - 2, rdd 4 (LoRaCodes.hpp:376-394) gives 8
+ *               symbols; binaryToGray16; << 2
+ *   the rest    the K = max(ND - (sf - 7), 0) data nibbles from index sf - 7 on, exactly as
+ *               lora_encode_chain_batch treats a payload except that the whitening starts at bit
+ *               offset sf - 7: codewords by rdd, zero codewords up to B * sf, B = ceil(K / sf),
+ *               whitening, diagonalInterleaveSx at PPM sf, binaryToGray16
+ *   symbols     nsym = 8 + B * (4 + rdd) per frame (the modulator adds its two sync symbols)
+ * Decode of a frame of which `avail` symbols are there:
+ *   avail < 8: status SHORT, every field 0.  Otherwise the header's symbols are rounded to the
+ *   nearest multiple of four bins, r = ((s + 2) >> 2) & (2^(sf-2) - 1) (a +-1 bin error is
+ *   absorbed), then grayToBinary16, diagonalDeterleaveSx at PPM sf - 2, rdd 4 (LoRaCodes.hpp:
+ *   396-412), decodeHamming84sx (LoRaCodes.hpp:250-281) of codewords 0..4.  The header is bad
+ *   (status HEADER, every field 0) when any of the five raised `bad`, when nibble 3 exceeds 1,
+ *   when headerChecksum({h0, h1}) differs from the received one, or when h1 >> 1 > 4.
+ *   Otherwise nbytes, rdd, has_crc and nsym are set, and errors counts the header's codewords
+ *   that raised `error` or `bad`.  Header-only mode ends here with status OK.
+ *   Full decode: nsym > avail (or nbytes > max_bytes) is status SHORT, the fields set, the
+ *   payload zeros.  Otherwise the inverse of the above gives D; errors also counts those of
+ *   the ND data codewords that flagged an error (Hamming 8/4's `bad` counts as one); status is
+ *   CRC when crc is set and the two received bytes differ from sx1272DataChecksum(P) - the
+ *   payload is written all the same - else OK.  Payload bytes beyond nbytes are written 0. */
+#define LORA_FRAME_OK 0
+#define LORA_FRAME_HEADER 1
+#define LORA_FRAME_SHORT 2
+#define LORA_FRAME_CRC 3
+
+/* nsym of a frame (above; headerChecksum's fields, LoRaCodes.hpp:43-67).  Host arithmetic
+ * only, no HIP call.  sf outside 7..12, rdd outside 0..4, nbytes outside 0..255 or crc outside
+ * {0, 1} is LORA_EINVAL, here and below. */
+int64_t lora_frame_symbols(int sf, int rdd, int64_t nbytes, int crc);
+
+/* Encode `frames` frames (the layout above; LoRaCodes.hpp:43-67, 92-105, 176-189, 229-371,
+ * 376-394).  payload [frames][payload_stride] holds up to max_bytes bytes per frame, of which
+ * frame f has nbytes[f] (device int32, clamped to 0..max_bytes; NULL: max_bytes each); rdd and
+ * crc are per call.  symbols [frames][sym_stride]: columns 0 .. S-1 are written, S =
+ * lora_frame_symbols(sf, rdd, max_bytes, crc), with 0 beyond the frame's own nsym; nsym[f]
+ * (optional) receives that count.  One kernel, nothing allocated or synchronised, parameters
+ * checked before any HIP call as for the codec above.  Returns S. */
+int64_t lora_encode_frame_batch(int sf, int rdd, int crc, const uint8_t* payload, int64_t frames, int64_t max_bytes,
+                                int64_t payload_stride, const int32_t* nbytes, uint16_t* symbols,
+                                int64_t sym_stride, int32_t* nsym, int device, void* stream);
+
+/* Decode `frames` frames (the decode above; LoRaCodes.hpp:43-67, 92-105, 176-189, 212-222,
+ * 250-365, 396-412) from symbols [frames][sym_stride], of which frame f has avail[f] (device
+ * int32, clamped to 0..sym_count; NULL: sym_count each).  Per frame, each optional: status
+ * (LORA_FRAME_*), nbytes, rdd, has_crc, nsym, errors (int32).  payload [frames][payload_stride]
+ * receives max_bytes (0..255) bytes per frame; a NULL payload selects header-only mode.  One
+ * kernel, nothing allocated or synchronised, every output fully written.  Returns max_bytes
+ * (0 in header-only mode). */
+int64_t lora_decode_frame_batch(int sf, const uint16_t* symbols, int64_t frames, int64_t sym_count,
+                                int64_t sym_stride, const int32_t* avail, int32_t* status, int32_t* nbytes,
+                                int32_t* rdd, int32_t* has_crc, int32_t* nsym, int32_t* errors, uint8_t* payload,
+                                int64_t max_bytes, int64_t payload_stride, int device, void* stream);
+
+/* Cut `slots` frames out of a stream: out[s][t] = flat[at[s] + t] for t < len[s], 0 for
+ * len[s] <= t < cut (complex64 as interleaved floats, as lora_demod_batch takes them,
+ * LoRaDemod.cpp:49-61; flat holds `total` samples).  at and len are device int64 arrays; a slot
+ * with at[s] < 0 or at[s] >= total is all zeros, len is clamped to 0..cut and to the stream's
+ * end: nothing at or beyond at[s] + len[s], or beyond flat + total, is read.  The zeros make a
+ * slot's demodulation a function of its frame alone.  flat is 8-byte aligned (a frame starts at
+ * any sample); out [slots][out_stride] and its rows are 16-byte aligned (out_stride even),
+ * out_stride >= cut, else LORA_EINVAL.  One kernel, nothing allocated or synchronised, columns
+ * 0 .. cut-1 of every row fully written.  Returns cut. */
+int64_t lora_gather_frames_batch(const float* flat, int64_t total, const int64_t* at, const int64_t* len,
+                                 int64_t slots, int64_t cut, float* out, int64_t out_stride, int device,
+                                 void* stream);
 
 /* Measurement hooks (bench.py): while enabled, every kernel lora_demod_batch launches
  * on this plan is bracketed by a pair of HIP events on the stream it runs on, for up

@@ -552,6 +552,233 @@ __global__ void __launch_bounds__(kBlock) k_codec_chain_encode(ChainArgs a) {
 }
 
 // ---------------------------------------------------------------------------------
+// Self-describing frames (the definition is in include/lora_mi355x.h)
+// ---------------------------------------------------------------------------------
+// Nothing is staged: a lane builds each symbol it writes (encoder) or each byte it writes
+// (decoder) from the codewords it needs, which it computes from the frame's bytes or symbols
+// in global memory - a frame is a few hundred bytes that stay in the cache - so the kernels
+// need no LDS and no barrier.  The header is eight symbols: every lane of a frame's group
+// decodes it for itself.
+
+// the remaining blocks' whitening starts sf - 7 bytes into the sequence: the last byte used is
+// ceil(K / sf) * sf + sf - 8 with K = 2 * 257 - (sf - 7) codewords
+constexpr bool frame_whiten_fits() {
+  for (int sf = 7; sf <= 12; ++sf)
+    if ((2 * (kMaxPayload + 2) - (sf - 7) + sf - 1) / sf * sf + (sf - 7) > kWhitenLen) return false;
+  return true;
+}
+static_assert(frame_whiten_fits(), "the whitening table must cover a frame of 255 bytes and its CRC");
+
+__host__ __device__ inline int frame_nsym(int sf, int rdd, int n, int crc) {
+  const int nd = 2 * (n + 2 * crc);
+  const int k = nd > sf - 7 ? nd - (sf - 7) : 0;
+  return 8 + (k + sf - 1) / sf * (4 + rdd);
+}
+
+// headerChecksum (LoRaCodes.hpp:43-67) of h0 | h1 << 8: each of its five bits is a parity
+__device__ __forceinline__ uint32_t header_checksum(uint32_t w) {
+  return (par(w & 0x0F0) << 4) | (par(w & 0x18E) << 3) | (par(w & 0xA49) << 2) | (par(w & 0x725) << 1) |
+         par(w & 0xF12);
+}
+
+struct FrameEncArgs {
+  int sf, rdd, crc, max_bytes;
+  int lg;    // 0..6
+  int cols;  // symbols written per row: those of a frame of max_bytes
+  int64_t frames, pay_stride, sym_stride;
+  const uint8_t* pay;
+  const int32_t* nbytes;  // NULL: max_bytes for every frame
+  uint16_t* sym;
+  int32_t* nsym;
+};
+
+// data nibble i of a frame of n payload bytes and checksum c (its low byte first), high nibble
+// of a byte first
+__device__ __forceinline__ uint32_t frame_nibble(const uint8_t* in, int n, uint32_t c, int i) {
+  const int k = i >> 1;
+  const uint32_t b = k < n ? in[k] : (k == n ? c & 0xFF : c >> 8);
+  return (i & 1) ? b & 0xF : b >> 4;
+}
+
+__global__ void __launch_bounds__(kBlock) k_frame_encode(FrameEncArgs a) {
+  const int tid = threadIdx.x;
+  const int G = 1 << a.lg;
+  const int l = tid & (G - 1);
+  const int64_t f = (int64_t)blockIdx.x * (kBlock >> a.lg) + (tid >> a.lg);
+  const bool live = f < a.frames;
+  const uint8_t* in = a.pay + (live ? f : 0) * a.pay_stride;
+  int n = 0;
+  if (live) n = a.nbytes ? min(max(a.nbytes[f], 0), a.max_bytes) : a.max_bytes;
+  uint32_t w = 0;
+  if (a.crc) {  // the checksum of all n bytes: byte k shifts n - 1 - k bytes (< 256: the table)
+    const int levels = crc_levels(n - 1);
+    for (int k = l; k < n; k += G) w ^= crc_term(in[k], (uint32_t)(n - 1 - k), levels);
+    w = crc_finish(group_xor(w, a.lg), n);
+  }
+  if (!live) return;
+  const int sf = a.sf, rdd = a.rdd, nbits = 4 + rdd, nh = sf - 7;
+  const int nd = 2 * (n + 2 * a.crc);
+  const int ns = frame_nsym(sf, rdd, n, a.crc);
+  const uint32_t h1 = (uint32_t)(rdd << 1) | (uint32_t)a.crc;
+  const uint32_t h2 = header_checksum((uint32_t)n | (h1 << 8));
+  // the header's nibbles, four bits each from bit 0
+  const uint32_t hw = ((uint32_t)n >> 4) | (((uint32_t)n & 15) << 4) | (h1 << 8) | ((h2 >> 4) << 12) | ((h2 & 15) << 16);
+  const uint8_t* wh = kWhiten.v[rdd == 1 ? 1 : 0];
+  const uint32_t mask = 0xFFu >> (4 - rdd);
+  uint16_t* row = a.sym + f * a.sym_stride;
+  for (int s = l; s < a.cols; s += G) {
+    uint32_t v = 0;
+    if (s < 8) {
+      // symbol `s` of block 0: its bit c is bit s of the block's codeword (c + s) mod (sf - 2)
+      // (LoRaCodes.hpp:376-394 at PPM sf - 2); Gray, then two bins per value step
+      const int ppm = sf - 2;
+      for (int c = 0; c < ppm; ++c) {
+        const int j = (c + s) % ppm;
+        uint32_t cw;
+        if (j < 5) {
+          cw = enc_h84((hw >> (4 * j)) & 15);
+        } else {
+          cw = j - 5 < nd ? enc_h84(frame_nibble(in, n, w, j - 5)) : 0u;
+          cw ^= kWhiten.v[0][j - 5];
+        }
+        v |= ((cw >> s) & 1u) << c;
+      }
+      v = (v ^ (v >> 1)) << 2;
+    } else if (s < ns) {
+      const int blk = (s - 8) / nbits;
+      const int bit = (s - 8) - blk * nbits;
+      for (int c = 0; c < sf; ++c) {
+        const int j = blk * sf + (c + bit) % sf;  // codeword of the remaining blocks
+        uint32_t cw = nh + j < nd ? nibble_encode(frame_nibble(in, n, w, nh + j), rdd) : 0u;
+        cw ^= wh[nh + j] & mask;
+        v |= ((cw >> bit) & 1u) << c;
+      }
+      v ^= v >> 1;
+    }
+    row[s] = (uint16_t)v;
+  }
+  if (l == 0 && a.nsym) a.nsym[f] = ns;
+}
+
+struct FrameDecArgs {
+  int sf, max_bytes;
+  int lg;    // 0..6
+  int cols;  // symbols per row
+  int64_t frames, sym_stride, pay_stride;
+  const uint16_t* sym;
+  const int32_t* avail;  // NULL: cols for every frame
+  int32_t *status, *nbytes, *rdd, *has_crc, *nsym, *errors;
+  uint8_t* pay;  // NULL: header-only mode
+};
+
+// codeword j of block 0 from its eight binary symbols: bit `bit` is bit (j - bit) mod ppm of
+// symbol `bit` (LoRaCodes.hpp:396-412 at PPM sf - 2)
+__device__ __forceinline__ uint32_t block0_codeword(const uint32_t (&hs)[8], int ppm, int j) {
+  uint32_t cw = 0;
+#pragma unroll
+  for (int bit = 0; bit < 8; ++bit) cw |= ((hs[bit] >> ((j + 2 * ppm - bit) % ppm)) & 1u) << bit;
+  return cw;
+}
+
+__global__ void __launch_bounds__(kBlock) k_frame_decode(FrameDecArgs a) {
+  const int tid = threadIdx.x;
+  const int G = 1 << a.lg;
+  const int l = tid & (G - 1);
+  const int64_t f = (int64_t)blockIdx.x * (kBlock >> a.lg) + (tid >> a.lg);
+  const bool live = f < a.frames;
+  const int sf = a.sf, nh = sf - 7;
+  const uint16_t* row = a.sym + (live ? f : 0) * a.sym_stride;
+  int av = 0;
+  if (live) av = a.avail ? min(max(a.avail[f], 0), a.cols) : a.cols;
+  int status = LORA_FRAME_SHORT, n = 0, rdd = 0, crc = 0, ns = 0;
+  uint32_t herr = 0;
+  uint32_t hs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (av >= 8) {
+    // the header's symbols: to the nearest multiple of four bins, Gray -> binary
+#pragma unroll
+    for (int i = 0; i < 8; ++i) hs[i] = gray_to_binary16((((uint32_t)row[i] + 2u) >> 2) & ((1u << (sf - 2)) - 1u));
+    uint32_t hw = 0, hbad = 0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const Nib d = dec_h84(block0_codeword(hs, sf - 2, j));
+      hw |= d.nib << (4 * j);
+      herr += d.err;  // set for a bad codeword too
+      hbad |= d.bad;
+    }
+    const uint32_t h0 = ((hw & 15) << 4) | ((hw >> 4) & 15), h1 = (hw >> 8) & 15;
+    const uint32_t h2 = (((hw >> 12) & 15) << 4) | ((hw >> 16) & 15);
+    if (hbad || h2 > 31 || header_checksum(h0 | (h1 << 8)) != h2 || (h1 >> 1) > 4) {
+      status = LORA_FRAME_HEADER;
+      herr = 0;
+    } else {
+      status = LORA_FRAME_OK;
+      n = (int)h0;
+      rdd = (int)(h1 >> 1);
+      crc = (int)(h1 & 1);
+      ns = frame_nsym(sf, rdd, n, crc);
+    }
+  }
+  uint32_t w = 0, ne = 0;  // w as in k_codec_decode: checksum terms low, received checksum high
+  if (a.pay) {
+    const bool whole = status == LORA_FRAME_OK && ns <= av && n <= a.max_bytes;
+    if (status == LORA_FRAME_OK && !whole) status = LORA_FRAME_SHORT;
+    if (live) {
+      const int nbits = 4 + rdd;
+      const int nd = whole ? n + 2 * crc : 0;  // data bytes to decode
+      const int levels = crc_levels(n - 1);
+      const uint8_t* wh = kWhiten.v[rdd == 1 ? 1 : 0];
+      const uint32_t mask = 0xFFu >> (4 - rdd);
+      uint8_t* out = a.pay + f * a.pay_stride;
+      for (int k = l; k < max(nd, a.max_bytes); k += G) {
+        if (k >= nd) {
+          out[k] = 0;
+          continue;
+        }
+        uint32_t byte = 0;
+        for (int h = 0; h < 2; ++h) {
+          const int i = 2 * k + h;  // data nibble
+          Nib d;
+          if (i < nh) {
+            d = dec_h84(block0_codeword(hs, sf - 2, 5 + i) ^ kWhiten.v[0][i]);
+          } else {
+            // codeword c = row `dst` of block `blk` of the remaining blocks, as in
+            // k_codec_chain_decode
+            const int c = i - nh;
+            const int blk = c / sf;
+            const int dst = c - blk * sf;
+            const uint16_t* s = row + 8 + blk * nbits;
+            uint32_t cw = 0;
+            for (int bit = 0; bit < nbits; ++bit)
+              cw |= ((gray_to_binary16(s[bit]) >> ((dst + 2 * sf - bit) % sf)) & 1u) << bit;
+            d = nibble_decode(cw ^ (wh[i] & mask), rdd);
+          }
+          byte = (byte << 4) | d.nib;
+          ne += d.err;
+        }
+        if (k < n) {
+          out[k] = (uint8_t)byte;
+          if (crc) w ^= crc_term(byte, (uint32_t)(n - 1 - k), levels);
+        } else {
+          w ^= byte << (k == n ? 16 : 24);
+          if (k < a.max_bytes) out[k] = 0;
+        }
+      }
+    }
+    w = group_xor(w, a.lg);
+    ne = group_sum(ne, a.lg);
+    if (whole && crc && crc_finish(w & 0xFFFF, n) != (w >> 16)) status = LORA_FRAME_CRC;
+  }
+  if (live && l == 0) {
+    if (a.status) a.status[f] = status;
+    if (a.nbytes) a.nbytes[f] = n;
+    if (a.rdd) a.rdd[f] = rdd;
+    if (a.has_crc) a.has_crc[f] = crc;
+    if (a.nsym) a.nsym[f] = ns;
+    if (a.errors) a.errors[f] = (int32_t)(herr + ne);
+  }
+}
+
+// ---------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------
 using lora::set_last_error;
@@ -722,4 +949,78 @@ int64_t lora_encode_chain_batch(int sf, int rdd, const uint8_t* payload, int64_t
   a.sym_out = symbols;
   if ((int64_t)(kBlock >> a.lg) * a.ncw > kChainEncLds) return set_last_error(LORA_EINVAL, "frame too long");
   return launch_frames(k_codec_chain_encode, a, frames, a.lg, device, stream, nsym);
+}
+
+namespace {
+bool frame_params_ok(int sf, int rdd, int64_t nbytes, int crc) {
+  return sf >= 7 && sf <= 12 && rdd >= 0 && rdd <= 4 && nbytes >= 0 && nbytes <= kMaxPayload && (crc == 0 || crc == 1);
+}
+const char* const kFrameParams = "sf must be in 7..12, rdd in 0..4, nbytes in 0..255, crc 0 or 1";
+}  // namespace
+
+int64_t lora_frame_symbols(int sf, int rdd, int64_t nbytes, int crc) {
+  if (!frame_params_ok(sf, rdd, nbytes, crc)) return set_last_error(LORA_EINVAL, kFrameParams);
+  return frame_nsym(sf, rdd, (int)nbytes, crc);
+}
+
+int64_t lora_encode_frame_batch(int sf, int rdd, int crc, const uint8_t* payload, int64_t frames, int64_t max_bytes,
+                                int64_t payload_stride, const int32_t* nbytes, uint16_t* symbols,
+                                int64_t sym_stride, int32_t* nsym, int device, void* stream) {
+  if (!frame_params_ok(sf, rdd, max_bytes, crc)) return set_last_error(LORA_EINVAL, kFrameParams);
+  if (frames < 0) return set_last_error(LORA_EINVAL, "bad frames");
+  const int64_t cols = frame_nsym(sf, rdd, (int)max_bytes, crc);
+  if (payload_stride < max_bytes) return set_last_error(LORA_EINVAL, "payload_stride smaller than max_bytes");
+  if (sym_stride < cols) return set_last_error(LORA_EINVAL, "sym_stride smaller than the symbols per frame");
+  if (frames == 0) return cols;
+  if (!symbols || (max_bytes > 0 && !payload)) return set_last_error(LORA_EINVAL, "null buffer");
+  FrameEncArgs a{};
+  a.sf = sf;
+  a.rdd = rdd;
+  a.crc = crc;
+  a.max_bytes = (int)max_bytes;
+  a.lg = group_lg(cols);
+  a.cols = (int)cols;
+  a.frames = frames;
+  a.pay_stride = payload_stride;
+  a.sym_stride = sym_stride;
+  a.pay = payload;
+  a.nbytes = nbytes;
+  a.sym = symbols;
+  a.nsym = nsym;
+  return launch_frames(k_frame_encode, a, frames, a.lg, device, stream, cols);
+}
+
+int64_t lora_decode_frame_batch(int sf, const uint16_t* symbols, int64_t frames, int64_t sym_count,
+                                int64_t sym_stride, const int32_t* avail, int32_t* status, int32_t* nbytes,
+                                int32_t* rdd, int32_t* has_crc, int32_t* nsym, int32_t* errors, uint8_t* payload,
+                                int64_t max_bytes, int64_t payload_stride, int device, void* stream) {
+  if (sf < 7 || sf > 12) return set_last_error(LORA_EINVAL, "sf must be in 7..12");
+  if (frames < 0 || sym_count < 0 || sym_count >= (int64_t(1) << 31))
+    return set_last_error(LORA_EINVAL, "bad frames / sym_count");
+  if (sym_stride < sym_count) return set_last_error(LORA_EINVAL, "sym_stride smaller than sym_count");
+  if (!payload) max_bytes = 0;  // header-only mode
+  if (max_bytes < 0 || max_bytes > kMaxPayload) return set_last_error(LORA_EINVAL, "max_bytes must be in 0..255");
+  if (payload && payload_stride < max_bytes)
+    return set_last_error(LORA_EINVAL, "payload_stride smaller than max_bytes");
+  if (frames == 0) return max_bytes;
+  if (sym_count > 0 && !symbols) return set_last_error(LORA_EINVAL, "null buffer");
+  if (!payload && !status && !nbytes && !rdd && !has_crc && !nsym && !errors) return max_bytes;  // nothing to write
+  FrameDecArgs a{};
+  a.sf = sf;
+  a.max_bytes = (int)max_bytes;
+  a.lg = payload ? group_lg(max_bytes + 2) : 0;
+  a.cols = (int)sym_count;
+  a.frames = frames;
+  a.sym_stride = sym_stride;
+  a.pay_stride = payload_stride;
+  a.sym = symbols;
+  a.avail = avail;
+  a.status = status;
+  a.nbytes = nbytes;
+  a.rdd = rdd;
+  a.has_crc = has_crc;
+  a.nsym = nsym;
+  a.errors = errors;
+  a.pay = payload;
+  return launch_frames(k_frame_decode, a, frames, a.lg, device, stream, max_bytes);
 }

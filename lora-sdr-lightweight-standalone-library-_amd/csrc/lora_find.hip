@@ -278,12 +278,245 @@ __global__ void __launch_bounds__(kThreads) k_find_frames(FindArgs a) {
   for (int64_t i = (done < a.capacity ? done : a.capacity) + tid; i < a.capacity; i += kThreads) starts[i] = -1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Frames that state their own length: the candidates are listed, their headers decoded
+// (lora_decode_frame_batch), and the pass runs over the slots whose header is good.
+// ---------------------------------------------------------------------------------------------
+
+// lora_find_candidates_batch: the candidate rule and refinement of build_tile, listed instead of
+// walked.  A candidate is eligible when its start lies in 0 .. last_start (here: the header's ten
+// symbols fit the row); it is listed unless its start equals the last listed one - which is the
+// start of the eligible candidate before it, listed or not, so the test is local.  One workgroup
+// takes a row, kThreads windows at a time: a ballot of the eligible, each eligible lane looks up
+// its predecessor's start (this wave's ballot, the waves before, the turn before), a ballot of
+// the listed, and the slot is the count so far plus the set bits below.  FindArgs as the finder's,
+// `first`, `end` and the jump's fields unused.
+__global__ void __launch_bounds__(kThreads) k_find_candidates(FindArgs a) {
+  __shared__ unsigned long long elig[kWaves], listed[kWaves];
+  __shared__ int64_t st[kThreads];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t row = blockIdx.x;
+  const float* pw = a.power + row * a.stride;
+  const float* pa = a.power_avg + row * a.stride;
+  const uint16_t* ix = a.index + row * a.stride;
+  int64_t* starts = a.starts + row * a.capacity;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  // uniform over the workgroup: listed so far, and the last eligible start of the turns before
+  int64_t cnt = 0, prev = -1;  // (no eligible start is negative)
+  for (int64_t base = 0; base < a.n; base += kThreads) {
+    const int64_t w = base + tid;
+    bool el = false;
+    int64_t s = -1;
+    if (w < a.n) {  // w + k < W
+      const int i0 = ix[w], i1 = ix[w + a.k];
+      const float p0 = pw[w], f0 = pa[w], p1 = pw[w + a.k], f1 = pa[w + a.k];
+      s = refined_start(a, w, i0);
+      el = p0 - f0 >= a.thresh && p1 - f1 >= a.thresh && ((i1 - i0) & (a.N - 1)) == a.dsync && s >= 0 &&
+           s <= a.last_start;
+    }
+    const unsigned long long m = __ballot(el);
+    st[tid] = s;
+    if (lane == 0) elig[wave] = m;
+    __syncthreads();
+    bool list = false;
+    if (el) {
+      int64_t ps = prev;
+      if (m & below) {
+        ps = st[wave * 64 + 63 - __clzll((long long)(m & below))];
+      } else {
+        int v = wave - 1;
+        while (v >= 0 && elig[v] == 0ull) --v;
+        if (v >= 0) ps = st[v * 64 + 63 - __clzll((long long)elig[v])];
+      }
+      list = ps != s;
+    }
+    const unsigned long long ml = __ballot(list);
+    if (lane == 0) listed[wave] = ml;
+    __syncthreads();
+    int before = 0, total = 0, lastw = -1;
+    for (int v = 0; v < kWaves; ++v) {
+      const int c = __popcll(listed[v]);
+      if (v < wave) before += c;
+      total += c;
+      if (elig[v] != 0ull) lastw = v;
+    }
+    if (list) {
+      const int64_t pos = cnt + before + __popcll(ml & below);
+      if (pos < a.capacity) starts[pos] = s;
+    }
+    if (lastw >= 0) prev = st[lastw * 64 + 63 - __clzll((long long)elig[lastw])];
+    cnt += total;
+    __syncthreads();  // st, elig and listed are rewritten by the next turn
+  }
+  if (tid == 0) a.count[row] = (int32_t)cnt;  // cnt <= n < 2^31
+  for (int64_t i = (cnt < a.capacity ? cnt : a.capacity) + tid; i < a.capacity; i += kThreads) starts[i] = -1;
+}
+
+// lora_select_frames_batch: the greedy pass over a row's slots, in slot order.  What makes a slot
+// eligible - a good header, a frame no longer than max_symbols that fits the row - does not
+// depend on the pass, so the workgroup tests kSelThreads slots at a time in parallel and one
+// lane walks the set bits alone, carrying `first`.
+constexpr int kSelThreads = 256;
+struct SelectArgs {
+  const int64_t* starts;   // [rows][slots]
+  const int32_t* status;   // [rows][slots]
+  const int32_t* nsym;     // [rows][slots]
+  const int64_t* first;    // [rows] or null
+  int64_t slots, row_len, step, capacity;
+  int max_symbols;
+  int64_t* out_starts;     // [rows][capacity]
+  int32_t* out_nsym;       // [rows][capacity]
+  int32_t* count;          // [rows]
+  int64_t* end;            // [rows]
+};
+
+__global__ void __launch_bounds__(kSelThreads) k_select_frames(SelectArgs a) {
+  __shared__ unsigned long long elig[kSelThreads / 64];
+  __shared__ int64_t st[kSelThreads];
+  __shared__ int32_t ns[kSelThreads];
+  __shared__ int64_t s_first, s_cnt;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t row = blockIdx.x;
+  int64_t* out_starts = a.out_starts + row * a.capacity;
+  int32_t* out_nsym = a.out_nsym + row * a.capacity;
+  if (tid == 0) {
+    s_first = a.first ? a.first[row] : 0;
+    s_cnt = 0;
+  }
+  for (int64_t base = 0; base < a.slots; base += kSelThreads) {
+    const int64_t j = base + tid;
+    bool el = false;
+    int64_t s = -1;
+    int32_t n = 0;
+    if (j < a.slots) {
+      s = a.starts[row * a.slots + j];
+      n = a.nsym[row * a.slots + j];
+      el = a.status[row * a.slots + j] == LORA_FRAME_OK && n >= 0 && n <= a.max_symbols && s >= 0 &&
+           s <= a.row_len - (2 + (int64_t)n) * a.step;
+    }
+    const unsigned long long m = __ballot(el);
+    st[tid] = s;
+    ns[tid] = n;
+    if (lane == 0) elig[wave] = m;
+    __syncthreads();
+    if (tid == 0) {
+      int64_t first = s_first, cnt = s_cnt;
+      for (int v = 0; v < kSelThreads / 64; ++v) {
+        for (unsigned long long b = elig[v]; b != 0ull; b &= b - 1) {
+          const int i = v * 64 + __ffsll((long long)b) - 1;
+          if (st[i] < first) continue;
+          if (cnt < a.capacity) {
+            out_starts[cnt] = st[i];
+            out_nsym[cnt] = ns[i];
+          }
+          ++cnt;
+          first = st[i] + (2 + (int64_t)ns[i]) * a.step;
+        }
+      }
+      s_first = first;
+      s_cnt = cnt;
+    }
+    __syncthreads();
+  }
+  __syncthreads();  // (no slots: s_first and s_cnt as tid 0 set them)
+  const int64_t done = s_cnt;
+  if (tid == 0) {
+    a.count[row] = (int32_t)done;  // done <= slots < 2^31
+    a.end[row] = s_first;
+  }
+  for (int64_t i = (done < a.capacity ? done : a.capacity) + tid; i < a.capacity; i += kSelThreads) {
+    out_starts[i] = -1;
+    out_nsym[i] = 0;
+  }
+}
+
 }  // namespace
 }  // namespace lora
 
 using lora::set_last_error;
 
 extern "C" {
+
+int64_t lora_find_candidates_batch(const lora_find_params* p, const float* power, const float* power_avg,
+                                   const uint16_t* index, int64_t rows, int64_t W, int64_t stride,
+                                   int64_t row_len, int64_t capacity, int64_t* starts, int32_t* count,
+                                   void* stream) {
+  if (!p) return set_last_error(LORA_EINVAL, "null params");
+  if (p->sf < 6 || p->sf > 12) return set_last_error(LORA_EINVAL, "the frame finder needs SF 6-12");
+  if (p->osr < 1 || p->osr > (1u << 16)) return set_last_error(LORA_EINVAL, "osr must be in 1..65536");
+  const int64_t N = int64_t(1) << p->sf, step = N * (int64_t)p->osr;
+  if (p->hop < 1 || step % p->hop != 0 || step / p->hop < 2)
+    return set_last_error(LORA_EINVAL, "hop must divide step = N * osr at least twice");
+  if (rows < 0 || W < 0 || stride < 0 || row_len < 0 || capacity < 0)
+    return set_last_error(LORA_EINVAL, "negative rows / W / stride / row_len / capacity");
+  if (W >= (int64_t(1) << 31)) return set_last_error(LORA_EINVAL, "W must be < 2^31");
+  if (rows >= (int64_t(1) << 31)) return set_last_error(LORA_EINVAL, "batch too large");
+  if (rows > 1 && stride < W) return set_last_error(LORA_EINVAL, "stride smaller than windows per row");
+  if (rows == 0) return 0;
+  if (!count || (capacity > 0 && !starts)) return set_last_error(LORA_EINVAL, "null output");
+  const int64_t k = step / p->hop;
+  if (W > k && (!power || !power_avg || !index)) return set_last_error(LORA_EINVAL, "null metrics");
+  lora::FindArgs a{};
+  a.power = power;
+  a.power_avg = power_avg;
+  a.index = index;
+  a.starts = starts;
+  a.count = count;
+  a.stride = stride;
+  a.capacity = capacity;
+  a.n = W - k;
+  a.hop = p->hop;
+  a.osr = p->osr;
+  a.half_step = step / 2;
+  a.frame_len = 10 * step;  // the two sync symbols and the header's eight
+  a.last_start = row_len - a.frame_len;
+  a.k = (int)k;
+  a.N = (int)N;
+  const int sync = (int)(p->sync & 0xFFu);
+  a.sw0 = (sync >> 4) << (p->sf - 4);
+  const int sw1 = (sync & 15) << (p->sf - 4);
+  a.dsync = (sw1 - a.sw0) & (a.N - 1);
+  a.thresh = p->thresh_db;
+  lora::DeviceGuard guard(p->device);
+  if (guard.err != hipSuccess) return lora::hip_error("find device", guard.err);
+  hipLaunchKernelGGL(lora::k_find_candidates, dim3((unsigned)rows), dim3(lora::kThreads), 0,
+                     static_cast<hipStream_t>(stream), a);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? lora::hip_error("k_find_candidates", e) : rows;
+}
+
+int64_t lora_select_frames_batch(const int64_t* cand_starts, const int32_t* status, const int32_t* nsym,
+                                 int64_t rows, int64_t slots, const int64_t* first, int64_t row_len, int64_t step,
+                                 int64_t max_symbols, int64_t capacity, int64_t* starts, int32_t* out_nsym,
+                                 int32_t* count, int64_t* end, int device, void* stream) {
+  if (rows < 0 || slots < 0 || row_len < 0 || capacity < 0 || step < 1 || max_symbols < 0)
+    return set_last_error(LORA_EINVAL, "negative rows / slots / row_len / capacity / max_symbols, or step < 1");
+  if (rows >= (int64_t(1) << 31) || slots >= (int64_t(1) << 31) || max_symbols >= (int64_t(1) << 31))
+    return set_last_error(LORA_EINVAL, "batch too large");
+  if (rows == 0) return 0;
+  if (!count || !end || (capacity > 0 && (!starts || !out_nsym))) return set_last_error(LORA_EINVAL, "null output");
+  if (slots > 0 && (!cand_starts || !status || !nsym)) return set_last_error(LORA_EINVAL, "null slots");
+  lora::SelectArgs a{};
+  a.starts = cand_starts;
+  a.status = status;
+  a.nsym = nsym;
+  a.first = first;
+  a.slots = slots;
+  a.row_len = row_len;
+  a.step = step;
+  a.capacity = capacity;
+  a.max_symbols = (int)max_symbols;
+  a.out_starts = starts;
+  a.out_nsym = out_nsym;
+  a.count = count;
+  a.end = end;
+  lora::DeviceGuard guard(device);
+  if (guard.err != hipSuccess) return lora::hip_error("select device", guard.err);
+  hipLaunchKernelGGL(lora::k_select_frames, dim3((unsigned)rows), dim3(lora::kSelThreads), 0,
+                     static_cast<hipStream_t>(stream), a);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? lora::hip_error("k_select_frames", e) : rows;
+}
 
 int64_t lora_find_frames_tile(void) { return lora::kFindTile; }
 

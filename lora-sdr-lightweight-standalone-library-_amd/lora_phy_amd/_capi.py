@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = (
     "lora_detect_scan_batch",
     "lora_find_frames_tile",
     "lora_find_frames_batch",
+    "lora_find_candidates_batch",
+    "lora_select_frames_batch",
     "lora_channelize_outputs",
     "lora_channelize_batch",
     "lora_resample_outputs",
@@ -65,6 +67,10 @@ EXPORTED_SYMBOLS = (
     "lora_decode_chain_soft_batch",
     "lora_encode_chain_batch",
     "lora_chain_symbols",
+    "lora_frame_symbols",
+    "lora_encode_frame_batch",
+    "lora_decode_frame_batch",
+    "lora_gather_frames_batch",
     "lora_demod_profile_enable",
     "lora_demod_profile_read",
     "lora_demod_last_kernels",
@@ -183,6 +189,15 @@ def lib() -> C.CDLL:
     L.lora_find_frames_batch.argtypes = [C.POINTER(FindParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
+    # the finder of self-describing frames: candidates listed, then selected by their headers
+    L.lora_find_candidates_batch.restype = C.c_int64
+    L.lora_find_candidates_batch.argtypes = [C.POINTER(FindParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                             C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]
+    L.lora_select_frames_batch.restype = C.c_int64
+    L.lora_select_frames_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                           C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     # the down-converter bank (csrc/lora_channelize.hip)
     L.lora_channelize_outputs.restype = C.c_int64
     L.lora_channelize_outputs.argtypes = [C.c_int64, C.c_int64, C.c_int64]
@@ -253,6 +268,19 @@ def lib() -> C.CDLL:
                                           C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     L.lora_chain_symbols.restype = C.c_int64
     L.lora_chain_symbols.argtypes = [C.c_int, C.c_int, C.c_int64]
+    # self-describing frames (csrc/lora_codec.hip) and the frame gather (csrc/lora_gather.hip)
+    L.lora_frame_symbols.restype = C.c_int64
+    L.lora_frame_symbols.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int]
+    L.lora_encode_frame_batch.restype = C.c_int64
+    L.lora_encode_frame_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+    L.lora_decode_frame_batch.restype = C.c_int64
+    L.lora_decode_frame_batch.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
+    L.lora_gather_frames_batch.restype = C.c_int64
+    L.lora_gather_frames_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                           C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     L.lora_demod_profile_enable.restype = C.c_int
     L.lora_demod_profile_enable.argtypes = [C.c_void_p, C.c_int]
     L.lora_demod_profile_read.restype = C.c_int

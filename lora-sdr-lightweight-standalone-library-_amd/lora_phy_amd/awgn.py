@@ -284,3 +284,117 @@ def sweep_receive(sf: int, snr_dbs: Sequence[float], frames: int = 2000, frame_s
                     "frame_symbols": S, "windows": noise_total, "false_starts": false,
                     "false_starts_per_million_windows": false * 1e6 / noise_total})
     return out
+
+
+# --------------------------------------------------------------------------------------
+# Self-describing frames of mixed lengths (stream.impair -> stream.receive_frames_device)
+# --------------------------------------------------------------------------------------
+
+def sweep_receive_frames(sf: int, snr_dbs: Sequence[float], frames: int = 1000, max_bytes: int = 16, cr=1,
+                         osr: int = 1, hop: Optional[int] = None, thresh_db: float = 0.0, seed: int = 1234,
+                         frames_per_row: int = 4, noise_windows: int = 0, noise_batch_samples: int = 1 << 26,
+                         sync: int = 0x12, device=None) -> List[Dict]:
+    """``sweep_receive`` for frames that state their own length: what ``stream.receive_frames_device``
+    returns under ``stream.impair``, with no frame length given to it.
+
+    Layout: ``ceil(frames / frames_per_row)`` zero rows, each with ``frames_per_row`` self-describing
+    frames (``codec.encode_frame`` at coding rate ``cr`` with the CRC, GPU ``modulate``, amplitude
+    1) whose payload lengths are drawn uniformly from 0 .. ``max_bytes`` - mixed lengths in every
+    row - at starts that are multiples of ``osr``, every frame after a gap drawn uniformly from
+    0 .. 2 * step - 1 chips (and one such gap behind the last).  The layout and the payloads are
+    drawn once from ``seed`` and serve every SNR point; the noise of point i is ``impair``'s with
+    this ``seed`` and ``first_row = i * rows``.  ``max_symbols`` is that of a ``max_bytes`` frame.
+
+    Per SNR point one record: ``planted``; ``returned_ok`` - planted frames returned at their exact
+    start with status OK and the exact payload (``p_ok``); ``found_at_planted`` - planted starts
+    among the returned, whatever their decode; ``false_frames`` - returned frames whose start was
+    not planted (``false_frames_per_million_windows``), ``false_frames_ok`` those of them whose
+    status is OK; ``candidates`` listed and ``candidates_dropped`` beyond the candidate capacity;
+    ``windows`` scanned.  With ``noise_windows > 0`` a last record (``"noise_only": True``) has the
+    candidates and the false frames over at least that many windows of noise alone.  Everything
+    runs on the device; the counts of all points come to the host in one copy at the end."""
+    from . import codec, stream
+
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    N = 1 << sf
+    step = N * osr
+    hop = step // 4 if hop is None else int(hop)
+    K, B = int(frames_per_row), int(max_bytes)
+    R = -(-int(frames) // K)
+    F = R * K
+    S = codec.frame_symbols(sf, cr, B)
+    rng = np.random.default_rng(seed)
+    nbytes = rng.integers(0, B + 1, (R, K))
+    nsym = np.vectorize(lambda n: codec.frame_symbols(sf, cr, int(n)))(nbytes)
+    length = (nsym + 2) * step                                                   # [R, K]
+    gaps = rng.integers(0, 2 * N, (R, K + 1)) * osr
+    starts = np.cumsum(gaps[:, :K], axis=1) + np.cumsum(length, axis=1) - length
+    L = int((starts[:, -1] + length[:, -1] + gaps[:, K]).max())
+    pay = rng.integers(0, 256, (F, B)).astype(np.uint8)
+    pay[np.arange(B)[None, :] >= nbytes.reshape(-1, 1)] = 0
+    plan = DemodPlan(sf, osr, 125000, "none", dechirp=True, mode="legacy", device=dev)
+    starts_t = torch.from_numpy(starts).to(dev)
+    pay_t = torch.from_numpy(pay).to(dev).view(R, K, B)
+    nbytes_t = torch.from_numpy(nbytes.astype(np.int32)).to(dev)
+    symbols, _ = codec.encode_frame(pay_t.view(F, B), nbytes_t.view(-1), sf, cr)
+    rows = modulate(symbols, sf, osr, 125000, 1.0, sync)                         # [F, (S + 2) * step]
+    clean = torch.zeros((R, L), dtype=torch.complex64, device=dev)
+    at = (torch.arange(R, device=dev)[:, None] * L + starts_t).reshape(-1)
+    live = torch.arange(rows.shape[1], device=dev)[None, :] < torch.from_numpy(length).to(dev).reshape(-1, 1)
+    clean.view(-1)[(at[:, None] + torch.arange(rows.shape[1], device=dev))[live]] = rows[live]
+    del rows, live
+    work = torch.empty_like(clean)
+    W = (L - step) // hop + 1
+    counts = []
+
+    def tally(got):
+        valid = got.found.valid                                                  # [R, cap]
+        cap = valid.shape[1]
+        same = got.found.starts[:, :, None] == starts_t[:, None, :]              # [R, cap, K]
+        hit = same.any(2) & valid
+        which = same.to(torch.int8).argmax(2)
+        ok = got.frames.status.view(R, cap) == codec.FRAME_OK
+        want = torch.gather(pay_t, 1, which[:, :, None].expand(-1, -1, B))
+        want_n = torch.gather(nbytes_t, 1, which)
+        rx = got.frames.payload.view(R, cap, got.frames.payload.shape[-1])[:, :, :B]
+        right = hit & ok & (got.frames.nbytes.view(R, cap) == want_n) & (rx == want).all(2)
+        C = got.found.starts.new_tensor(-(-L // (4 * step)))
+        return torch.stack([right.sum(), hit.sum(), (valid & ~hit).sum(), (valid & ~hit & ok).sum(),
+                            got.candidates.sum(), (got.candidates.to(torch.int64) - C).clamp_min(0).sum()])
+
+    for i, snr in enumerate(snr_dbs):
+        stream.impair(clean, snr_db=float(snr), seed=seed, first_row=i * R, out=work)
+        counts.append(tally(stream.receive_frames_device(plan, work, S, hop, sync, thresh_db)))
+    noise_counts, noise_total = [], 0
+    if noise_windows > 0:
+        Ln = max((S + 3) * step, min(int(noise_batch_samples), 1 << 22))
+        Rn = max(1, int(noise_batch_samples) // Ln)
+        Wn = (Ln - step) // hop + 1
+        Cn = -(-Ln // (4 * step))
+        buf = torch.empty((Rn, Ln), dtype=torch.complex64, device=dev)
+        b = 0
+        while noise_total < noise_windows:
+            stream.impair(None, sigma=1.0, seed=seed + 1, first_row=b * Rn, out=buf, rows=Rn, length=Ln, device=dev)
+            got = stream.receive_frames_device(plan, buf, S, hop, sync, thresh_db)
+            ok = (got.frames.status.view(Rn, -1) == codec.FRAME_OK) & got.found.valid
+            noise_counts.append(torch.stack([got.found.count.sum(), ok.sum(), got.candidates.sum(),
+                                             (got.candidates.to(torch.int64) - Cn).clamp_min(0).sum()]))
+            noise_total += Rn * Wn
+            b += 1
+    got = torch.stack(counts).cpu().numpy() if counts else np.zeros((0, 6), np.int64)  # the synchronisation
+    out = []
+    for snr, (right, hit, false, false_ok, cands, dropped) in zip(snr_dbs, got.tolist()):
+        out.append({"sf": sf, "osr": osr, "snr_db": float(snr), "hop": hop, "thresh_db": float(thresh_db),
+                    "max_bytes": B, "max_symbols": S, "rdd": codes.rdd_of(cr), "planted": F, "returned_ok": right,
+                    "found_at_planted": hit, "false_frames": false, "false_frames_ok": false_ok,
+                    "candidates": cands, "candidates_dropped": dropped, "windows": R * W, "p_ok": right / F,
+                    "false_frames_per_million_windows": false * 1e6 / (R * W)})
+    if noise_counts:
+        false, false_ok, cands, dropped = torch.stack(noise_counts).sum(0).cpu().tolist()
+        out.append({"sf": sf, "osr": osr, "noise_only": True, "hop": hop, "thresh_db": float(thresh_db),
+                    "max_symbols": S, "windows": noise_total, "false_frames": false, "false_frames_ok": false_ok,
+                    "candidates": cands, "candidates_dropped": dropped,
+                    "candidates_per_window": cands / noise_total,
+                    "candidate_capacity_per_window": hop / (4 * step),
+                    "false_frames_per_million_windows": false * 1e6 / noise_total})
+    return out

@@ -9,6 +9,16 @@ the checker in the tests.
 
 Symbols are uint16 tensors, payloads uint8 tensors, [F, n] or 1-D for a single frame.  Rows
 may be strided views (unit stride within a row, rows not overlapping).
+
+Self-describing frames (``encode_frame``, ``decode_header``, ``decode_frame`` over
+lora_encode_frame_batch / lora_decode_frame_batch) put an explicit header in front of the chain:
+the payload length, the coding rate and a CRC flag under the reference's 5-bit header checksum,
+as five Hamming 8/4 codewords in a first block of eight symbols at rate 4/8 whose values are
+multiples of four bins (a +-1 bin error is absorbed), and with the flag the SX1272 data checksum
+of the whole payload behind it.  Rows of one batch may hold frames of different lengths and
+coding rates; a decode needs no length from its caller.  The layout is this project's own (the
+reference has the two checksums, no header), stated to the bit in include/lora_mi355x.h and
+restated in numpy in tests/frame_checker.py.  SF 7-12.
 """
 from __future__ import annotations
 
@@ -204,3 +214,123 @@ def decode_chain_soft(llr: torch.Tensor, sf: int, cr, nbytes: int, out: Optional
                                                          nbytes, _ptr(pay), _row_stride(pay),
                                                          out.errors.data_ptr(), dev.index, _stream(dev)))
     return out
+
+
+# ---------------------------------------------------------------------------------
+# Self-describing frames (include/lora_mi355x.h, "Self-describing frames")
+# ---------------------------------------------------------------------------------
+FRAME_OK, FRAME_HEADER, FRAME_SHORT, FRAME_CRC = 0, 1, 2, 3
+FRAME_MIN_SF = 7  # the header block carries sf - 7 data nibbles
+
+
+@dataclass
+class FrameResult:
+    """Per-frame results of ``decode_frame`` / ``decode_header`` (int32 [F] tensors on the
+    symbols' device).  ``status`` is FRAME_OK, FRAME_HEADER (bad header: every field 0),
+    FRAME_SHORT (fewer than 8 symbols: every field 0; or fewer than the header's ``nsym``: the
+    fields set, the payload zeros) or FRAME_CRC (the payload is written all the same)."""
+
+    status: torch.Tensor
+    nbytes: torch.Tensor             # payload bytes the header states
+    rdd: torch.Tensor                # its coding rate, 4 / (4 + rdd)
+    has_crc: torch.Tensor            # its CRC flag
+    nsym: torch.Tensor               # data symbols of the whole frame
+    errors: torch.Tensor             # header and data codewords whose decode flagged an error
+    payload: Optional[torch.Tensor]  # [F, max_bytes] uint8, zeros beyond nbytes; None: header only
+
+    _FIELDS = ("status", "nbytes", "rdd", "has_crc", "nsym", "errors")
+
+
+def frame_symbols(sf: int, cr, nbytes: int, crc: bool = True) -> int:
+    """Data symbols of a self-describing frame of ``nbytes`` payload bytes: 8 of the header
+    block, then ceil(K / sf) blocks of 4 + RDD with K = max(2 * (nbytes + 2 * crc) - (sf - 7), 0)
+    (host arithmetic; SF 7-12)."""
+    return _capi.check(_capi.lib().lora_frame_symbols(int(sf), codes.rdd_of(cr), int(nbytes), int(bool(crc))))
+
+
+def frame_capacity(sf: int, nsymbols: int) -> int:
+    """The most payload bytes a frame of ``nsymbols`` data symbols can state (rate 4/4, no
+    CRC): the payload width ``decode_frame`` needs for rows of that many symbols."""
+    if nsymbols < 8:
+        return 0
+    return min(MAX_PAYLOAD, ((nsymbols - 8) // 4 * int(sf) + int(sf) - FRAME_MIN_SF) // 2)
+
+
+def _per_frame(t: Optional[torch.Tensor], name: str, F: int, device: torch.device):
+    if t is None:
+        return None
+    _check_buf(t, name, torch.int32, device, F)
+    if t.dim() != 1 or t.shape[0] != F:
+        raise ValueError(f"{name} must be an int32 [{F}] tensor")
+    return t.data_ptr() if F > 0 else None
+
+
+def encode_frame(payload: torch.Tensor, nbytes: Optional[torch.Tensor], sf: int, cr, crc: bool = True,
+                 out: Optional[torch.Tensor] = None, out_nsym: Optional[torch.Tensor] = None):
+    """Self-describing frames on the device (lora_encode_frame_batch): ``payload`` is uint8
+    [F, max_bytes] (or [max_bytes]), of which frame f uses ``nbytes[f]`` bytes (int32 [F] on the
+    device, clamped to 0..max_bytes; None: max_bytes each).  The header states nbytes, the coding
+    rate and the CRC flag; with ``crc`` the SX1272 data checksum of the whole payload follows it.
+    Returns ``(symbols, nsym)``: uint16 [F, S] with S = frame_symbols(sf, cr, max_bytes, crc),
+    zeros beyond each frame's own count, and that count, int32 [F]."""
+    rdd = codes.rdd_of(cr)
+    p, squeeze = _rows(payload, "payload", torch.uint8)
+    F, n = p.shape
+    lib = _capi.lib()
+    S = _capi.check(lib.lora_frame_symbols(int(sf), rdd, n, int(bool(crc))))
+    o = _out_rows(out, "out", torch.uint16, F, S, squeeze, p.device)
+    if out_nsym is None:
+        out_nsym = torch.empty(F, dtype=torch.int32, device=p.device)
+    _capi.check(lib.lora_encode_frame_batch(int(sf), rdd, int(bool(crc)), _ptr(p), F, n, _row_stride(p),
+                                            _per_frame(nbytes, "nbytes", F, p.device), _ptr(o), _row_stride(o),
+                                            _per_frame(out_nsym, "out_nsym", F, p.device), p.device.index,
+                                            _stream(p.device)))
+    return (o[0] if squeeze else o), out_nsym
+
+
+def _decode_frames(symbols, sf, avail, max_bytes, out, header_only):
+    s, squeeze = _symbols(symbols)
+    F, S = s.shape
+    dev = s.device
+    if header_only:
+        max_bytes = 0
+    elif max_bytes is None:
+        max_bytes = frame_capacity(sf, S)
+    max_bytes = int(max_bytes)
+    if not 0 <= max_bytes <= MAX_PAYLOAD:
+        raise ValueError(f"max_bytes must be in 0..{MAX_PAYLOAD}")
+    if out is None:
+        fields = {k: torch.empty(F, dtype=torch.int32, device=dev) for k in FrameResult._FIELDS}
+        pay = None if header_only else torch.empty((max_bytes,) if squeeze else (F, max_bytes), dtype=torch.uint8,
+                                                   device=dev)
+        out = FrameResult(payload=pay, **fields)
+    ptrs = [_per_frame(getattr(out, k), "out." + k, F, dev) for k in FrameResult._FIELDS]
+    pay_ptr, pay_stride = None, 0
+    if not header_only:
+        # the library reads a NULL payload as header-only mode: a zero-width payload still has
+        # a (never dereferenced) address of its own
+        pay = _out_rows(out.payload, "out.payload", torch.uint8, F, max_bytes, squeeze, dev)
+        pay_ptr, pay_stride = (pay.data_ptr() or out.status.data_ptr()), _row_stride(pay)
+    _capi.check(_capi.lib().lora_decode_frame_batch(int(sf), _ptr(s), F, S, _row_stride(s),
+                                                    _per_frame(avail, "avail", F, dev), *ptrs, pay_ptr,
+                                                    max_bytes, pay_stride, dev.index, _stream(dev)))
+    return out
+
+
+def decode_header(symbols: torch.Tensor, sf: int, avail: Optional[torch.Tensor] = None,
+                  out: Optional[FrameResult] = None) -> FrameResult:
+    """The header of each row of ``symbols`` (uint16 [F, S] or [S]; only the first 8 are read):
+    status FRAME_OK with nbytes, rdd, has_crc, nsym and the header's error count, FRAME_HEADER,
+    or FRAME_SHORT when fewer than 8 symbols are there (``avail``: int32 [F] on the device,
+    None: S each).  ``payload`` is None."""
+    return _decode_frames(symbols, sf, avail, None, out, True)
+
+
+def decode_frame(symbols: torch.Tensor, sf: int, avail: Optional[torch.Tensor] = None,
+                 max_bytes: Optional[int] = None, out: Optional[FrameResult] = None) -> FrameResult:
+    """Self-describing frames -> payloads (lora_decode_frame_batch): each row's header gives its
+    length, coding rate and CRC flag, so rows of one batch may hold different frames.  ``avail``:
+    how many of a row's S symbols belong to the frame (int32 [F] on the device, clamped to 0..S;
+    None: S each).  ``max_bytes``: the payload's width, by default ``frame_capacity(sf, S)``, the
+    most a frame of S symbols can hold (a frame stating more than max_bytes is FRAME_SHORT)."""
+    return _decode_frames(symbols, sf, avail, max_bytes, out, False)

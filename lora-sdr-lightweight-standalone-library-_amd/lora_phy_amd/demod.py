@@ -538,6 +538,38 @@ class LoRaDemod:
         R, cap = got.found.starts.shape
         return got.found, got.result.symbols.reshape(R, cap, got.result.symbols.shape[1])[:, :, :self.mtu]
 
+    def work_packets_device(self, iq: torch.Tensor, max_symbols: Optional[int] = None, hop: Optional[int] = None,
+                            thresh_db: float = 0.0, first=None, capacity: Optional[int] = None,
+                            cand_capacity: Optional[int] = None):
+        """Receive self-describing frames (``LoRaMod.work_frame``) from a [L] stream or [R, L] rows
+        with no frame length given (``lora_phy_amd.stream.receive_frames_device`` with this block's
+        plan and sync word): each frame's header states its length, coding rate and CRC flag, and
+        the header's coding rate wins over this block's ``cr``.  ``max_symbols``: the longest frame
+        accepted, by default ``mtu``.  Returns the stream.StreamPackets - ``found``, ``nsym``, and
+        ``frames`` with every slot's status and payload; select with ``found.valid``.  ``last``
+        keeps the DemodResult of all slots.  Nothing synchronises."""
+        from . import stream
+
+        got = stream.receive_frames_device(self.plan, iq, self.mtu if max_symbols is None else max_symbols, hop,
+                                           self.sync, thresh_db, first, capacity, cand_capacity)
+        self.last = got.result
+        return got
+
+    def work_wideband_packets_device(self, chan, iq: torch.Tensor, max_symbols: Optional[int] = None,
+                                     hop: Optional[int] = None, thresh_db: float = 0.0,
+                                     scale: Optional[float] = None, first=None, capacity: Optional[int] = None,
+                                     cand_capacity: Optional[int] = None):
+        """``work_packets_device`` for a wideband capture
+        (``lora_phy_amd.stream.receive_wideband_frames_device``): row r of the result is channel r
+        of ``chan``, starts are in channel samples.  Nothing synchronises."""
+        from . import stream
+
+        got = stream.receive_wideband_frames_device(self.plan, chan, iq, self.mtu if max_symbols is None
+                                                    else max_symbols, hop, self.sync, thresh_db, scale, first,
+                                                    capacity, cand_capacity)
+        self.last = got.result
+        return got
+
     def sync_ok(self) -> torch.Tensor:
         """Per-frame flag: recovered sync word equals the configured one."""
         if self.last is None:

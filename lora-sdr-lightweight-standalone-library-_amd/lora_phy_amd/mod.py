@@ -79,6 +79,27 @@ class LoRaMod:
             frames = frames.unsqueeze(0)
         return stream.transmit_wideband(synth, frames, channel, starts, chan_len, dtype=dtype)
 
+    def work_frame(self, payload, nbytes=None, crc: bool = True) -> torch.Tensor:
+        """Self-describing frames (``codec.encode_frame`` at this block's ``sf`` and ``cr``), then
+        modulated: ``payload`` is uint8 [F, max_bytes] (or [max_bytes]), of which frame f carries
+        ``nbytes[f]`` bytes (an int32 [F] tensor or a sequence; None: max_bytes each).  Every row
+        is as long as the longest possible frame; a shorter frame is followed by silence - zero
+        samples, not zero symbols - so a receiver sees nothing after its last symbol.  Nothing is
+        read back: the frame lengths stay on the device.  (SF 7-12.)"""
+        from . import codec
+
+        if not isinstance(payload, torch.Tensor):
+            payload = torch.as_tensor(payload, dtype=torch.uint8)
+        payload = payload.to(self.device)
+        if nbytes is not None:
+            nbytes = torch.as_tensor(nbytes, dtype=torch.int32).to(self.device).reshape(-1)
+        symbols, nsym = codec.encode_frame(payload, nbytes, self.sf, self.cr, crc=crc)
+        iq = self.work(symbols)
+        step = (1 << self.sf) * self.ovs
+        live = torch.arange(iq.shape[-1], device=self.device) < ((nsym.to(torch.int64) + 2) * step)[:, None]
+        zero = torch.zeros((), dtype=iq.dtype, device=self.device)
+        return torch.where(live if iq.dim() == 2 else live[0], iq, zero)
+
     def work_payload(self, payload, chain: str = "library", append_crc: bool = False) -> torch.Tensor:
         """Encode payload bytes ([F, n] or [n] uint8) on the device (lora_phy_amd.codec), then
         modulate.  ``chain="library"``: lora_encode (LoRaEncoder.cpp:8-19), with

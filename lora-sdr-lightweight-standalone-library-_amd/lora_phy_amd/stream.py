@@ -52,6 +52,35 @@ device, in a fixed number of slots per row with a count beside them (``FoundFram
 device memory on the host - so the next chunk can be enqueued before anyone looks at this one's
 count.  The outputs equal the host finder's as integers.
 
+Frames that state their own length.  Everything above takes ``frame_symbols`` from its caller,
+so one call receives one kind of traffic.  ``receive_frames_device`` receives self-describing
+frames (``codec.encode_frame``: an explicit header with the payload length, the coding rate and
+a CRC flag under a 5-bit checksum, in a first block of eight symbols) of any mix of lengths and
+coding rates, and is given only ``max_symbols``, the longest frame it should accept.  The
+candidate rule and refinement above are unchanged; what changes is what happens to a candidate:
+
+* ``find_candidates_device`` lists, per row and in increasing w, each candidate's ``start`` with
+  ``start >= 0`` and ``start + 10 * step <= row_len``, unless it equals the row's last listed one
+  (``cand_capacity`` slots per row, ``ceil(row_len / (4 * step))`` by default, a count beside them);
+* ``gather_frames_device`` cuts ``10 * step`` samples at each, ``plan.run`` demodulates them and
+  ``codec.decode_header`` decodes the eight symbols: a status and, when the header is good, the
+  frame's ``nsym``;
+* ``select_frames_device`` is the greedy pass over the slots, in slot order: slot j is accepted
+  when its status is OK, ``nsym <= max_symbols``, ``start >= first`` and ``start + (2 + nsym) * step
+  <= row_len``, and ``first`` becomes that end.  (The fixed-length rule's jump to ``first - step /
+  2`` is implied: ``|d * osr| <= step / 2``.)  The result is a ``FoundFrames`` plus each frame's
+  ``nsym``;
+* a second gather cuts ``(2 + max_symbols) * step`` samples per slot, of which ``(2 + nsym) *
+  step`` are the frame's and the rest zeros, so a slot's demodulation is a function of its frame
+  alone; ``plan.run``; ``codec.decode_frame`` with ``avail = nsym``.
+
+Of 20,000 random 8-symbol headers per SF, 2 to 5 pass the header's checks, so the header is also
+the guard against false candidates that a negative ``thresh_db`` admits - the experiment the
+measurement above left open; DESIGN.md §6n has what was measured.  Limits: bw 125 kHz and the
+``hop`` rules as above, SF 7-12 (the header block carries ``sf - 7`` data nibbles), hard decisions
+only, no implicit-header mode, no preamble or SFD, and no claim of decoding a real LoRa radio.
+The host model of the chain lives in tests/frame_checker.py.
+
 Wideband captures.  An SDR delivers one wideband stream that holds several LoRa channels at
 known offsets from the tuner frequency.  ``Channelizer`` is the stage in front of the scan: one
 kernel mixes every channel down, low-pass filters and decimates it (lora_channelize_batch; the
@@ -103,7 +132,8 @@ from .demod import DemodPlan, DemodResult, DetectMetrics, _check_iq, _require_cu
 __all__ = ["find_frames", "extract_frames", "receive", "lowpass_taps", "nco_table", "Channelizer",
            "receive_wideband", "raw_scale", "raw_to_complex", "Synthesizer", "transmit_wideband",
            "FoundFrames", "StreamFrames", "find_frames_device", "receive_device", "receive_wideband_device",
-           "impair", "cfo_word", "noise_sigma"]
+           "impair", "cfo_word", "noise_sigma", "gather_frames_device", "StreamPackets", "find_candidates_device",
+           "select_frames_device", "receive_frames_device", "receive_wideband_frames_device"]
 
 _NONE = -(1 << 62)  # "no candidate here" in the packed starts
 
@@ -731,6 +761,277 @@ def receive_wideband_device(plan: DemodPlan, chan: "Channelizer", iq: torch.Tens
     _geometry(hop, plan.sf, plan.osr, frame_symbols, sync, plan.bw)
     rows = chan.run(iq, scale=scale)  # [C, Wc]
     return _receive_rows(plan, rows, frame_symbols, hop, sync, thresh_db, first, capacity)
+
+
+@dataclass
+class StreamPackets:
+    """``receive_frames_device``'s result for R rows with ``capacity`` slots each; ``result`` and
+    ``frames`` hold all ``R * capacity`` slots in row-major order (slot j of row r is frame
+    ``r * capacity + j``).  Only the slots of ``found.valid`` mean anything."""
+
+    found: FoundFrames        # count [R], starts [R, capacity], end [R]: as find_frames_device's
+    nsym: torch.Tensor        # [R, capacity] int32: each frame's data symbols by its header, 0 in empty slots
+    result: DemodResult       # of every slot cut to (2 + max_symbols) * step, zeros after its frame
+    frames: "object"          # codec.FrameResult of every slot: status, nbytes, rdd, has_crc, errors, payload
+    candidates: torch.Tensor  # [R] int32: candidates listed per row (above cand_capacity: some were dropped)
+
+
+def _scan_rows(metrics: DetectMetrics, what: str):
+    """power, power_avg, index as [R, W] and their shared row stride, checked as the finder needs."""
+    power, floor, index = metrics.power, metrics.power_avg, metrics.index
+    if not all(isinstance(t, torch.Tensor) for t in (power, floor, index)):
+        raise TypeError(f"{what} needs metrics with power, power_avg and index")
+    if power.dim() == 1:
+        power, floor, index = power.unsqueeze(0), floor.unsqueeze(0), index.unsqueeze(0)
+    if power.dim() != 2 or floor.shape != power.shape or index.shape != power.shape:
+        raise ValueError(f"{what} takes power, power_avg and index of one [W] or [R, W] shape")
+    if power.dtype != torch.float32 or floor.dtype != torch.float32 or index.dtype != torch.uint16:
+        raise TypeError("power and power_avg must be float32 and index uint16")
+    for t, name in ((power, "power"), (floor, "power_avg"), (index, "index")):
+        _require_cuda(t, "metrics." + name)
+    R, W = power.shape
+    if floor.device != power.device or index.device != power.device:
+        raise ValueError(f"power_avg and index must be on {power.device}, where power is")
+    if W > 1 and any(t.stride(1) != 1 for t in (power, floor, index)):
+        raise ValueError("the metrics must have unit column stride")
+    strides = {t.stride(0) for t in (power, floor, index)} if R > 1 else {W}
+    if len(strides) != 1 or min(strides) < W:
+        raise ValueError("power, power_avg and index must share one row stride >= W")
+    return power, floor, index, strides.pop()
+
+
+def find_candidates_device(metrics: DetectMetrics, hop: int, sf: int, osr: int, sync: int = 0x12,
+                           thresh_db: float = 0.0, row_len: Optional[int] = None,
+                           cand_capacity: Optional[int] = None, bw: int = 125000):
+    """The finder's candidates, listed on the device (lora_find_candidates_batch, one kernel): the
+    candidate rule and refinement of this module's docstring, unchanged, and per row, in
+    increasing w, every refined start with ``start >= 0`` and ``start + 10 * step <= row_len``
+    (two sync symbols and a header fit) that differs from the row's last listed one.
+
+    Returns ``(count, starts)``: int32 [R] - the starts listed, which may exceed the capacity -
+    and int64 [R, cand_capacity], -1 beyond the count.  ``cand_capacity`` defaults to
+    ``ceil(row_len / (4 * step))``.  Nothing synchronises."""
+    N, step, k, sw0, sw1, head_len = _geometry(hop, sf, osr, 8, sync, bw)
+    hop, osr = int(hop), step // N
+    power, floor, index, stride = _scan_rows(metrics, "find_candidates_device")
+    R, W = power.shape
+    if row_len is None:
+        row_len = (W - 1) * hop + step if W else 0
+    row_len = int(row_len)
+    cap = _ceil_div(row_len, 4 * step) if cand_capacity is None else int(cand_capacity)
+    if row_len < 0 or cap < 0:
+        raise ValueError("row_len and cand_capacity must be >= 0")
+    dev = power.device
+    count = torch.empty(R, dtype=torch.int32, device=dev)
+    starts = torch.empty((R, cap), dtype=torch.int64, device=dev)
+    if R:
+        prm = _capi.FindParams(int(sf), osr, int(sync) & 0xFF, float(thresh_db), hop, 8, dev.index)
+        _capi.check(_capi.lib().lora_find_candidates_batch(
+            _capi.C.byref(prm), power.data_ptr(), floor.data_ptr(), index.data_ptr(), R, W, stride, row_len, cap,
+            starts.data_ptr() if cap else None, count.data_ptr(), _stream_handle(dev)))
+    return count, starts
+
+
+def select_frames_device(cand_starts: torch.Tensor, status: torch.Tensor, nsym: torch.Tensor, step: int,
+                         row_len: int, max_symbols: int, first: Union[None, int, torch.Tensor] = None,
+                         capacity: Optional[int] = None) -> Tuple[FoundFrames, torch.Tensor]:
+    """The greedy pass over candidates whose headers were decoded (lora_select_frames_batch, one
+    kernel).  ``cand_starts`` int64, ``status`` and ``nsym`` int32, all [R, C] and contiguous on
+    one device: ``find_candidates_device``'s starts and ``codec.decode_header``'s results for the
+    frame cut at each.  In slot order, slot j is accepted when its status is FRAME_OK, ``nsym <=
+    max_symbols``, ``start >= first`` (an empty slot, -1, never is) and ``start + (2 + nsym) *
+    step <= row_len``; ``first`` then becomes that end.  ``first`` and ``capacity`` as
+    ``find_frames_device``'s (capacity defaults to ``row_len // (10 * step)``).
+
+    Returns ``(found, nsym)``: a FoundFrames of the same meaning, and int32 [R, capacity], each
+    accepted frame's data symbols, 0 in empty slots.  Nothing synchronises."""
+    for t, name, dt in ((cand_starts, "cand_starts", torch.int64), (status, "status", torch.int32),
+                        (nsym, "nsym", torch.int32)):
+        _require_cuda(t, name)
+        if t.dtype != dt:
+            raise TypeError(f"{name} must be {dt}, got {t.dtype}")
+        if t.dim() != 2 or t.shape != cand_starts.shape or t.device != cand_starts.device or not t.is_contiguous():
+            raise ValueError("cand_starts, status and nsym must be contiguous [R, C] tensors on one device")
+    R, C = cand_starts.shape
+    dev = cand_starts.device
+    step, row_len, max_symbols = int(step), int(row_len), int(max_symbols)
+    first_t = _find_first(first, R, dev)
+    if first_t is not None and first_t.device != dev:
+        raise ValueError(f"first must be on {dev}")
+    capacity = row_len // (10 * step) if capacity is None else int(capacity)
+    if capacity < 0:
+        raise ValueError("capacity must be >= 0")
+    found = FoundFrames(count=torch.empty(R, dtype=torch.int32, device=dev),
+                        starts=torch.empty((R, capacity), dtype=torch.int64, device=dev),
+                        end=torch.empty(R, dtype=torch.int64, device=dev))
+    out_nsym = torch.empty((R, capacity), dtype=torch.int32, device=dev)
+    if R:
+        if first_t is not None and not first_t.is_contiguous():
+            first_t = first_t.contiguous()
+        _capi.check(_capi.lib().lora_select_frames_batch(
+            cand_starts.data_ptr() if C else None, status.data_ptr() if C else None, nsym.data_ptr() if C else None,
+            R, C, first_t.data_ptr() if first_t is not None else None, row_len, step, max_symbols, capacity,
+            found.starts.data_ptr() if capacity else None, out_nsym.data_ptr() if capacity else None,
+            found.count.data_ptr(), found.end.data_ptr(), dev.index, _stream_handle(dev)))
+    return found, out_nsym
+
+
+def _receive_frame_rows(plan: DemodPlan, rows: torch.Tensor, max_symbols, hop, sync, thresh_db, first, capacity,
+                        cand_capacity) -> StreamPackets:
+    """The nine steps of ``receive_frames_device`` on [R, L] rows (checked by the caller)."""
+    from . import codec
+
+    sf, step, dev = plan.sf, plan.step, plan.device
+    max_symbols = int(max_symbols)
+    if sf < codec.FRAME_MIN_SF:
+        raise ValueError("self-describing frames need SF 7-12")
+    if max_symbols < 8:
+        raise ValueError("max_symbols must be >= 8: a frame has at least its header's eight symbols")
+    R, L = rows.shape
+    head_len, cut = 10 * step, (2 + max_symbols) * step
+    if L >= step:
+        met = plan.scan(rows, hop)
+    else:  # (no window: nothing to scan, and the kernels only have their outputs to fill)
+        met = DetectMetrics(*(torch.empty((R, 0), dtype=dt, device=dev)
+                              for dt in (torch.float32, torch.float32, torch.float32, torch.uint16)))
+    ccount, cstarts = find_candidates_device(met, hop, sf, plan.osr, sync, thresh_db, L, cand_capacity, plan.bw)
+    C = cstarts.shape[1]
+    # the rows as one stream (row r begins at r * row stride); an empty slot stays negative
+    rs = rows.stride(0) if R > 1 else L
+    flat = rows.as_strided(((R - 1) * rs + L,), (1,)) if R else rows.reshape(-1)
+    row0 = (torch.arange(R, device=dev) * rs)[:, None]
+    if R * C:
+        at = torch.where(cstarts >= 0, cstarts + row0, cstarts).reshape(-1)
+        heads = gather_frames_device(flat, at, torch.full_like(at, head_len), head_len)
+        hdr = codec.decode_header(plan.run(heads).symbols, sf)
+        status, hsym = hdr.status.view(R, C), hdr.nsym.view(R, C)
+    else:
+        status = hsym = torch.empty((R, C), dtype=torch.int32, device=dev)
+    found, nsym = select_frames_device(cstarts, status, hsym, step, L, max_symbols, first, capacity)
+    cap = found.starts.shape[1]
+    max_bytes = codec.frame_capacity(sf, max_symbols)
+    if R * cap == 0:
+        none = {k: torch.empty(0, dtype=torch.int32, device=dev) for k in codec.FrameResult._FIELDS}
+        frames = codec.FrameResult(payload=torch.empty((0, max_bytes), dtype=torch.uint8, device=dev), **none)
+        return StreamPackets(found, nsym, _no_frames(max_symbols, dev), frames, ccount)
+    at = torch.where(found.starts >= 0, found.starts + row0, found.starts).reshape(-1)
+    length = (nsym.reshape(-1).to(torch.int64) + 2) * step
+    res = plan.run(gather_frames_device(flat, at, length, cut))
+    frames = codec.decode_frame(res.symbols, sf, avail=nsym.reshape(-1), max_bytes=max_bytes)
+    return StreamPackets(found, nsym, res, frames, ccount)
+
+
+def receive_frames_device(plan: DemodPlan, iq: torch.Tensor, max_symbols: int, hop: Optional[int] = None,
+                          sync: int = 0x12, thresh_db: float = 0.0, first: Union[None, int, torch.Tensor] = None,
+                          capacity: Optional[int] = None, cand_capacity: Optional[int] = None) -> StreamPackets:
+    """Receive self-describing frames (``codec.encode_frame``, ``LoRaMod.work_frame``) of any mix
+    of lengths and coding rates from a [L] stream or [R, L] rows, with no frame length given and
+    without the host: nothing is read back, nothing synchronises, every shape comes from host
+    integers.  The steps: ``plan.scan``; ``find_candidates_device``; a gather of ``10 * step``
+    samples per candidate; ``plan.run``; ``codec.decode_header``; ``select_frames_device`` (the
+    greedy pass, over the candidates whose header is good, each frame as long as its header
+    says); a gather of ``(2 + max_symbols) * step`` samples per slot, of which ``(2 + nsym) *
+    step`` are the frame's and the rest zeros; ``plan.run``; ``codec.decode_frame`` with ``avail =
+    nsym``.  The zeros make a slot's demodulation that of its frame alone (``plan.run`` on the
+    frame zero-padded to the cut): the max-amplitude normalisation and the offset estimate see
+    no neighbour's samples.
+
+    ``max_symbols`` (>= 8): the longest frame accepted, in data symbols; a header that states
+    more is passed over.  ``first`` and ``capacity`` as ``find_frames_device``'s; ``capacity``
+    defaults to ``L // (10 * step)``, the most frames a row can hold - the second gather then
+    holds ``R * capacity * (2 + max_symbols) * step`` samples, up to ``(2 + max_symbols) / 10``
+    times the input, so a caller who knows their traffic passes a smaller one and watches
+    ``found.count > capacity``.  ``cand_capacity`` defaults to ``ceil(L / (4 * step))`` (the first
+    gather: ``R * cand_capacity * 10 * step`` samples, 2.5 times the input); ``candidates >
+    cand_capacity`` tells that some were not probed.  The header is the guard against false
+    candidates, so ``thresh_db`` may be negative here.
+
+    Returns StreamPackets: ``found`` and ``nsym``, the DemodResult of ALL slots and their frame
+    decode (``frames.status`` FRAME_OK / FRAME_CRC, ``frames.payload`` [R * capacity, max bytes of
+    a max_symbols frame]); select with ``found.valid``.  A chunked caller overlaps chunks by
+    ``(2 + max_symbols) * step - 1`` samples and carries ``found.end`` exactly as with
+    ``receive_device``.  Limits, inherited from the finder: bw 125 kHz, ``hop`` dividing ``step``
+    at least twice, and SF 7-12 (the header block)."""
+    if not plan.dechirp:
+        raise ValueError("receive_frames_device needs a plan with dechirp=True: the finder reads dechirped peaks")
+    if not isinstance(iq, torch.Tensor) or iq.dim() not in (1, 2):
+        raise ValueError("receive_frames_device takes one [L] stream or [R, L] rows")
+    hop = plan.step // 4 if hop is None else int(hop)
+    _geometry(hop, plan.sf, plan.osr, 8, sync, plan.bw)
+    return _receive_frame_rows(plan, _check_iq(iq, plan.device), max_symbols, hop, sync, thresh_db, first, capacity,
+                               cand_capacity)
+
+
+def receive_wideband_frames_device(plan: DemodPlan, chan: "Channelizer", iq: torch.Tensor, max_symbols: int,
+                                   hop: Optional[int] = None, sync: int = 0x12, thresh_db: float = 0.0,
+                                   scale: Optional[float] = None, first: Union[None, int, torch.Tensor] = None,
+                                   capacity: Optional[int] = None,
+                                   cand_capacity: Optional[int] = None) -> StreamPackets:
+    """``receive_frames_device`` for a wideband capture: ``chan.run`` on the [L] complex64 stream
+    (or the raw [L, 2] integer stream, converted with ``scale``), then the same steps over the
+    [C, Wc] channel rows - row r of the result is channel r, starts are in CHANNEL samples, and
+    ``first`` ([C]) and the capacities count per channel with ``row_len = Wc``.  Channels may
+    carry frames of different lengths at once.  No synchronisation."""
+    if not plan.dechirp:
+        raise ValueError("receive_wideband_frames_device needs a plan with dechirp=True: the finder reads "
+                         "dechirped peaks")
+    if not isinstance(iq, torch.Tensor) or iq.dim() != (2 if _is_raw(iq) else 1):
+        raise ValueError("receive_wideband_frames_device takes one [L] stream (raw samples: [L, 2])")
+    if chan.device != plan.device:
+        raise ValueError(f"the channelizer is on {chan.device}, the plan is on {plan.device}")
+    hop = plan.step // 4 if hop is None else int(hop)
+    _geometry(hop, plan.sf, plan.osr, 8, sync, plan.bw)
+    rows = chan.run(iq, scale=scale)  # [C, Wc]
+    return _receive_frame_rows(plan, rows, max_symbols, hop, sync, thresh_db, first, capacity, cand_capacity)
+
+
+def gather_frames_device(iq: torch.Tensor, at: torch.Tensor, length: torch.Tensor, cut: int,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Cut frames of different lengths out of a stream, on the device (lora_gather_frames_batch,
+    one kernel): ``out[s, t] = flat[at[s] + t]`` for ``t < length[s]`` and 0 up to ``cut``.
+
+    ``iq`` is a [L] complex64 CUDA stream, or [R, L] rows as ``scan`` takes them, read as the one
+    flat stream in which sample t of row r is ``r * iq.stride(0) + t``.  ``at`` and ``length``
+    are int64 [K] tensors on its device - the finder's starts and ``(2 + nsym) * step``, never
+    read on the host.  A slot with ``at < 0`` (the finder's empty slot) is all zeros; ``length``
+    is clamped to ``0..cut`` and to the stream's end, so nothing at or beyond ``at + length`` is
+    read.  The zeros after a frame make its demodulation a function of the frame alone: it
+    equals ``plan.run`` on the frame zero-padded to ``cut`` whatever follows it in the stream.
+
+    Returns complex64 [K, cut]; its rows are 16-byte aligned, so with an odd ``cut`` they are
+    ``cut + 1`` samples apart (``plan.run`` takes such rows).  ``out``: a tensor of that layout to
+    write into.  Nothing synchronises."""
+    iq = _check_iq(iq, iq.device if isinstance(iq, torch.Tensor) else None)
+    dev = iq.device
+    cut = int(cut)
+    if cut < 0:
+        raise ValueError("cut must be >= 0")
+    for t, name in ((at, "at"), (length, "length")):
+        _require_cuda(t, name)
+        if t.dtype != torch.int64:
+            raise TypeError(f"{name} must be an int64 tensor, got {t.dtype}")
+        if t.dim() != 1 or t.device != dev:
+            raise ValueError(f"{name} must be a 1-D tensor on {dev}")
+    K = at.shape[0]
+    if length.shape[0] != K:
+        raise ValueError("at and length must have one entry per slot")
+    at, length = at.contiguous(), length.contiguous()
+    R, L = iq.shape
+    total = (R - 1) * iq.stride(0) + L if R > 1 else L * min(R, 1)
+    pitch = cut + (cut & 1)
+    if out is None:
+        out = torch.empty((K, pitch), dtype=torch.complex64, device=dev)[:, :cut]
+    else:
+        _require_cuda(out, "out")
+        if (out.dtype != torch.complex64 or out.device != dev or tuple(out.shape) != (K, cut)
+                or (cut > 1 and out.stride(1) != 1) or (K > 1 and (out.stride(0) < cut or out.stride(0) & 1))
+                or out.data_ptr() & 15):
+            raise ValueError(f"out must be a complex64 [{K}, {cut}] tensor on {dev} with 16-byte aligned rows")
+    if K and cut:
+        _capi.check(_capi.lib().lora_gather_frames_batch(
+            iq.data_ptr() if total else None, total, at.data_ptr(), length.data_ptr(), K, cut, out.data_ptr(),
+            out.stride(0) if K > 1 else pitch, dev.index, _stream_handle(dev)))
+    return out
 
 
 # raw output dtypes of the synthesis bank: the default inv_scale (exact in fp32)
