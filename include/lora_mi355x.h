@@ -218,6 +218,29 @@ int64_t lora_demod_soft_bits_batch(lora_demod_plan* plan, const float* iq, int64
                                    const float* time_offset, const float* max_amp,
                                    float* llr, int64_t llr_stride, void* stream);
 
+/* lora_demod_soft_bits_batch for self-describing frames ("Self-describing frames", below):
+ * columns red_first .. red_first + red_count - 1 of every frame are REDUCED, the others are
+ * exactly lora_demod_soft_bits_batch's.  A reduced column is a symbol of a frame's header block,
+ * which carries sf - 2 bits in multiples of four bins and is rounded to the nearest one
+ * (r = ((s + 2) >> 2) & (2^(sf-2) - 1), then grayToBinary16, LoRaCodes.hpp:212-222).  With Q as
+ * above:
+ *   v'(k) = grayToBinary16(((k + 2) >> 2) & (2^(sf-2) - 1));
+ *   for c < sf - 2: m1 = max{Q[k] : bit c of v'(k) = 1}, m0 = max{Q[k] : bit c of v'(k) = 0},
+ *     llr[c] = (m1 == m0) ? +0.0f : m1 - m0;
+ *   llr[sf-2] = llr[sf-1] = +0.0f.
+ * (Bit c of v'(k) is bit c + 2 of grayToBinary16((k + 2) mod N): a reduced column is bits
+ * 2 .. sf-1 of the spectrum rotated by two bins.)  Maxima are exact in any order, so the values
+ * are reproducible to the bit, as the full-rate ones.  With the sync symbols in columns 0 and 1
+ * of a LEGACY / API frame its header is columns 2 .. 9: red_first = 2, red_count = 8.
+ * LORA_EINVAL, before any HIP call: everything lora_demod_soft_bits_batch refuses, a negative
+ * red_first or red_count, red_first + red_count > total, and red_count > 0 on a plan with
+ * sf < 7.  red_count == 0 is lora_demod_soft_bits_batch itself, bit for bit.  Returns total. */
+int64_t lora_demod_soft_bits_frame_batch(lora_demod_plan* plan, const float* iq, int64_t frames,
+                                         int64_t frame_len, int64_t frame_stride, const float* cfo,
+                                         const float* time_offset, const float* max_amp,
+                                         float* llr, int64_t llr_stride, int64_t red_first,
+                                         int64_t red_count, void* stream);
+
 /* Sliding detector scan of continuous streams: LoRaDetector<float>::detect
  * (LoRaDetector.hpp:39-74) on a window of step = N*osr samples that starts every `hop` samples
  * of each of `rows` rows of `row_len` complex samples (row r at iq + 2*r*row_stride floats).
@@ -754,6 +777,52 @@ int64_t lora_decode_frame_batch(int sf, const uint16_t* symbols, int64_t frames,
                                 int64_t sym_stride, const int32_t* avail, int32_t* status, int32_t* nbytes,
                                 int32_t* rdd, int32_t* has_crc, int32_t* nsym, int32_t* errors, uint8_t* payload,
                                 int64_t max_bytes, int64_t payload_stride, int device, void* stream);
+
+/* lora_decode_frame_batch on soft bits.  llr is [frames][sym_stride][sf] floats, the DATA columns
+ * of a frame (lora_demod_soft_bits_frame_batch's layout with red_first = 2, red_count = 8; pass
+ * llr + 2*sf): column 0 is the first header symbol and columns 0 .. 7 hold the reduced form.
+ * avail, status, nbytes, rdd, has_crc, nsym, payload, max_bytes and header-only mode (a NULL
+ * payload) are lora_decode_frame_batch's.  For a frame of which `avail` columns are there:
+ *   avail < 8: status SHORT, every field 0, hdr_flips 0.  Otherwise
+ *   block 0     L0[(c + bit) % (sf-2)][bit] = llr[bit][c], bit < 8, c < sf - 2
+ *               (diagonalDeterleaveSx at PPM sf - 2, LoRaCodes.hpp:396-412, on LLRs); for
+ *               codewords j >= 5 the sign of L0[j][b] is flipped where bit b of byte j - 5 of
+ *               Sx1272ComputeWhiteningLfsr (bit offset 0, rdd 4, LoRaCodes.hpp:176-189) is set;
+ *               the header's five are not flipped
+ *   a codeword  of nb LLRs L[0 .. nb-1] at rate 4/(4 + r), nb = 4 + r: maximum likelihood over
+ *               its 16 codewords with lora_decode_chain_soft_batch's metric - m(x) starts at
+ *               +0.0f and, for b = 0 .. nb-1 in this order, m = m + (bit b of e(x) ? L[b] :
+ *               -L[b]) in fp32, no contraction; x is scanned upward from best = -inf with a
+ *               strict '>', so the lowest nibble wins a tie and a NaN metric never wins.  Its
+ *               hard word is bit b = L[b] > 0.  Any float is a valid LLR; no NaN is written
+ *   header      codewords 0 .. 4 of block 0 at r = 4 (Hamming 8/4, LoRaCodes.hpp:229-242) give
+ *               the five nibbles; hdr_flips = the bit positions in which the five chosen
+ *               codewords differ from their hard words (0 .. 40).  The header is bad (status
+ *               HEADER, every field 0, hdr_flips still written) when nibble 3 exceeds 1, when
+ *               headerChecksum({h0, h1}) (LoRaCodes.hpp:43-67) differs from the received one,
+ *               when h1 >> 1 > 4, or when hdr_flips > max_flips.  (The hard gate tolerates one
+ *               flipped bit in each of five codewords: max_flips = 5 is its like.  Without a
+ *               limit the ML decoder maps every noise word to a codeword and only the 5-bit
+ *               checksum is left to refuse it.)  Otherwise nbytes, rdd, has_crc and nsym are
+ *               set; header-only mode ends here with status OK
+ *   full decode nsym > avail (or nbytes > max_bytes) is status SHORT, the fields set, the payload
+ *               zeros.  Otherwise data nibbles 0 .. sf-8 are codewords 5 onward of block 0 (r =
+ *               4), and the others come from columns 8 .. nsym-1 exactly as
+ *               lora_decode_chain_soft_batch treats a chain at the header's rdd, except that the
+ *               whitening starts at bit offset sf - 7.  Nibbles, the CRC comparison, CRC and OK
+ *               are lora_decode_frame_batch's; payload bytes beyond nbytes are written 0
+ *   corrected   codewords whose chosen codeword differs from the hard word: among the header's
+ *               five, plus (after a full decode) among the first ND data codewords; 0 with a bad
+ *               header
+ * hdr_flips (optional) int32 per frame.  max_flips outside 0 .. 40 is LORA_EINVAL; the other
+ * parameter checks are lora_decode_frame_batch's.  One kernel, nothing allocated or
+ * synchronised, no workspace, every output fully written.  This definition is the library's
+ * own: the reference has no soft path.  Returns max_bytes (0 in header-only mode). */
+int64_t lora_decode_frame_soft_batch(int sf, const float* llr, int64_t frames, int64_t sym_count,
+                                     int64_t sym_stride, const int32_t* avail, int32_t* status, int32_t* nbytes,
+                                     int32_t* rdd, int32_t* has_crc, int32_t* nsym, int32_t* corrected,
+                                     int32_t* hdr_flips, int max_flips, uint8_t* payload, int64_t max_bytes,
+                                     int64_t payload_stride, int device, void* stream);
 
 /* Cut `slots` frames out of a stream: out[s][t] = flat[at[s] + t] for t < len[s], 0 for
  * len[s] <= t < cut (complex64 as interleaved floats, as lora_demod_batch takes them,

@@ -1740,10 +1740,12 @@ int64_t lora_demod_metrics_batch(lora_demod_plan* plan, const float* iq, int64_t
   return rc < 0 ? rc : total;
 }
 
-int64_t lora_demod_soft_bits_batch(lora_demod_plan* plan, const float* iq, int64_t frames,
-                                   int64_t frame_len, int64_t frame_stride, const float* cfo,
-                                   const float* time_offset, const float* max_amp,
-                                   float* llr, int64_t llr_stride, void* stream) {
+// lora_demod_soft_bits_batch (red_count == 0 and red_first == 0) and
+// lora_demod_soft_bits_frame_batch: one validation, the launch by red_count
+static int64_t soft_bits_entry(lora_demod_plan* plan, const float* iq, int64_t frames, int64_t frame_len,
+                               int64_t frame_stride, const float* cfo, const float* time_offset,
+                               const float* max_amp, float* llr, int64_t llr_stride, int64_t red_first,
+                               int64_t red_count, void* stream) {
   if (!plan) return set_error(LORA_EINVAL, "null argument");
   if (frames < 0 || frame_len < 0 || frame_stride < 0 || llr_stride < 0)
     return set_error(LORA_EINVAL, "negative frames / frame_len / frame_stride / llr_stride");
@@ -1757,6 +1759,9 @@ int64_t lora_demod_soft_bits_batch(lora_demod_plan* plan, const float* iq, int64
   }
   const int64_t total = frame_len / plan->step;
   if (llr && llr_stride < total) return set_error(LORA_EINVAL, "llr_stride smaller than symbols per frame");
+  if (red_first < 0 || red_count < 0 || red_first > total || red_count > total - red_first)
+    return set_error(LORA_EINVAL, "the reduced columns must lie in 0 .. symbols per frame");
+  if (red_count > 0 && p.sf < 7) return set_error(LORA_EINVAL, "reduced columns need a plan with sf in 7..12");
   if (frames > 0) {
     if (!iq) return set_error(LORA_EINVAL, "null iq");
     if (p.mode != LORA_MODE_RAW && (!cfo || !time_offset))
@@ -1771,9 +1776,28 @@ int64_t lora_demod_soft_bits_batch(lora_demod_plan* plan, const float* iq, int64
   a.total = (int)total;
   a.mode = p.mode;
   a.dechirp = (p.mode != LORA_MODE_API && p.dechirp) ? 1 : 0;
-  const int rc = lora::launch_soft_bits(a, cfo, time_offset, max_amp, llr, llr_stride, frames,
-                                        static_cast<hipStream_t>(stream));
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = red_count > 0 ? lora::launch_soft_bits_frame(a, cfo, time_offset, max_amp, llr, llr_stride, frames,
+                                                              red_first, red_count, st)
+                               : lora::launch_soft_bits(a, cfo, time_offset, max_amp, llr, llr_stride, frames, st);
   return rc < 0 ? rc : total;
+}
+
+int64_t lora_demod_soft_bits_batch(lora_demod_plan* plan, const float* iq, int64_t frames,
+                                   int64_t frame_len, int64_t frame_stride, const float* cfo,
+                                   const float* time_offset, const float* max_amp,
+                                   float* llr, int64_t llr_stride, void* stream) {
+  return soft_bits_entry(plan, iq, frames, frame_len, frame_stride, cfo, time_offset, max_amp, llr, llr_stride, 0, 0,
+                         stream);
+}
+
+int64_t lora_demod_soft_bits_frame_batch(lora_demod_plan* plan, const float* iq, int64_t frames,
+                                         int64_t frame_len, int64_t frame_stride, const float* cfo,
+                                         const float* time_offset, const float* max_amp,
+                                         float* llr, int64_t llr_stride, int64_t red_first, int64_t red_count,
+                                         void* stream) {
+  return soft_bits_entry(plan, iq, frames, frame_len, frame_stride, cfo, time_offset, max_amp, llr, llr_stride,
+                         red_first, red_count, stream);
 }
 
 int64_t lora_detect_scan_windows(const lora_demod_plan* plan, int64_t row_len, int64_t hop) {

@@ -1,6 +1,8 @@
 // lora_codec.hip — the payload codec on the device: symbols <-> bytes for whole batches of
 // frames, behind lora_decode_batch / lora_encode_batch / lora_decode_chain_batch /
-// lora_encode_chain_batch / lora_decode_chain_soft_batch (include/lora_mi355x.h).
+// lora_encode_chain_batch / lora_decode_chain_soft_batch (include/lora_mi355x.h), and the
+// self-describing frame's lora_encode_frame_batch / lora_decode_frame_batch /
+// lora_decode_frame_soft_batch further down.
 //
 // The first four are bit-exact integer work, one kernel per call, no workspace, no atomics:
 //   k_codec_decode        LoRaDecoder.cpp:8-19 + the CRC check of phy.cpp:241-256
@@ -778,6 +780,165 @@ __global__ void __launch_bounds__(kBlock) k_frame_decode(FrameDecArgs a) {
   }
 }
 
+// k_frame_decode on soft bits (lora_decode_frame_soft_batch): the same layout - a group of lanes
+// per frame, nothing staged, every lane decodes the header for itself - with every codeword's
+// LLRs gathered through the deinterleave maps straight from global memory, as
+// k_soft_chain_decode gathers them.
+//
+// The coding rate comes from the header, so it differs between the frames of a wave.  One
+// decoder serves every rate: a codeword is always eight LLRs, those beyond its 4 + rdd bits +0.0
+// (adding +-0 to a metric that starts at +0.0 leaves every bit of it), and the 16 candidates
+// are selected by rdd.  Signs are flipped with XOR on the sign bit - what fp32 negation is -
+// so neither the whitening nor the candidates' bits cost a lane mask.  (Five inlined per-RDD
+// loops behind a switch, with selects for the signs, spilled 80 scalar registers.)  One
+// instance per SF: the row pitch and the two interleaver widths are constants.
+struct FrameSoftArgs {
+  int max_bytes, max_flips;
+  int lg;    // 0..6
+  int cols;  // columns per row
+  int64_t frames, sym_stride, pay_stride;
+  const float* llr;      // [frames][sym_stride][sf]
+  const int32_t* avail;  // NULL: cols for every frame
+  int32_t *status, *nbytes, *rdd, *has_crc, *nsym, *corrected, *hdr_flips;
+  uint8_t* pay;  // NULL: header-only mode
+};
+
+// Codeword j of a block of width md (sf - 2 or sf) whose first row is s: bit `bit` < 4 + rdd is
+// column (j - bit) mod md of row `bit`, its sign flipped where the whitening byte wb has the bit
+// set.  Returns the nibble whose codeword at rate 4 / (4 + rdd) has the largest metric
+// (k_soft_chain_decode's: fp32 additions in bit order from +0.0, scanned upward with a strict
+// '>'), and in `diff` that codeword XOR the hard word (bit = LLR > 0).
+template <int SF>
+__device__ __forceinline__ uint32_t soft_codeword(const float* __restrict__ s, int md, int j, uint32_t wb, int rdd,
+                                                  uint32_t& diff) {
+  const int nbits = 4 + rdd;
+  float L[8];
+  uint32_t hard = 0;
+#pragma unroll
+  for (int bit = 0; bit < 8; ++bit) {
+    // a bit beyond the codeword reads the codeword's last row (which is there) and is zeroed
+    const int rb = bit < 4 ? bit : min(bit, nbits - 1);
+    int col = j - rb;  // (j - rb) mod md without a division: j - rb >= -7 >= -2 md + 3
+    col += col < 0 ? md : 0;
+    col += col < 0 ? md : 0;
+    uint32_t u = __float_as_uint(s[rb * SF + col]);
+    u ^= ((wb >> bit) & 1u) << 31;
+    if (bit >= 4) u &= (uint32_t)((bit - nbits) >> 31);  // all ones where bit < nbits
+    const float v = __uint_as_float(u);
+    hard |= (v > 0.0f ? 1u : 0u) << bit;
+    L[bit] = v;
+  }
+  const bool parity = rdd == 1;  // the one rate whose code is not a prefix of Hamming 8/4
+  const uint32_t emask = 0xFFu >> (4 - rdd);
+  float best = -__builtin_inff();
+  uint32_t nib = 0, chosen = 0;
+#pragma unroll
+  for (uint32_t x = 0; x < 16; ++x) {
+    const uint32_t e = parity ? nibble_encode(x, 1) : enc_h84(x) & emask;
+    float m = 0.0f;
+#pragma unroll
+    for (int bit = 0; bit < 8; ++bit) m = m + __uint_as_float(__float_as_uint(L[bit]) ^ (((~e >> bit) & 1u) << 31));
+    if (m > best) {
+      best = m;
+      nib = x;
+      chosen = e;
+    }
+  }
+  diff = chosen ^ hard;
+  return nib;
+}
+
+template <int SF>
+__global__ void __launch_bounds__(kBlock) k_frame_decode_soft(FrameSoftArgs a) {
+  const int tid = threadIdx.x;
+  const int G = 1 << a.lg;
+  const int l = tid & (G - 1);
+  const int64_t f = (int64_t)blockIdx.x * (kBlock >> a.lg) + (tid >> a.lg);
+  const bool live = f < a.frames;
+  constexpr int sf = SF;
+  const float* __restrict__ row = a.llr + (live ? f : 0) * a.sym_stride * sf;
+  int av = 0;
+  if (live) av = a.avail ? min(max(a.avail[f], 0), a.cols) : a.cols;
+  int status = LORA_FRAME_SHORT, n = 0, rdd = 0, crc = 0, ns = 0;
+  uint32_t hcorr = 0, flips = 0;
+  if (av >= 8) {
+    uint32_t hw = 0;
+#pragma unroll 1
+    for (int j = 0; j < 5; ++j) {
+      uint32_t diff;
+      hw |= soft_codeword<SF>(row, SF - 2, j, 0u, 4, diff) << (4 * j);
+      hcorr += diff != 0 ? 1u : 0u;
+      flips += (uint32_t)__popc(diff);
+    }
+    const uint32_t h0 = ((hw & 15) << 4) | ((hw >> 4) & 15), h1 = (hw >> 8) & 15;
+    const uint32_t h2 = (((hw >> 12) & 15) << 4) | ((hw >> 16) & 15);
+    if (h2 > 31 || header_checksum(h0 | (h1 << 8)) != h2 || (h1 >> 1) > 4 || flips > (uint32_t)a.max_flips) {
+      status = LORA_FRAME_HEADER;
+      hcorr = 0;
+    } else {
+      status = LORA_FRAME_OK;
+      n = (int)h0;
+      rdd = (int)(h1 >> 1);
+      crc = (int)(h1 & 1);
+      ns = frame_nsym(sf, rdd, n, crc);
+    }
+  }
+  uint32_t w = 0, nc = 0;  // w as in k_codec_decode: checksum terms low, received checksum high
+  if (a.pay) {
+    const bool whole = status == LORA_FRAME_OK && ns <= av && n <= a.max_bytes;
+    if (status == LORA_FRAME_OK && !whole) status = LORA_FRAME_SHORT;
+    if (live) {
+      const int nbits = 4 + rdd, nh = SF - 7;
+      const int nd = whole ? n + 2 * crc : 0;  // data bytes to decode
+      const int levels = crc_levels(n - 1);
+      const uint8_t* wh = kWhiten.v[rdd == 1 ? 1 : 0];
+      const uint32_t mask = 0xFFu >> (4 - rdd);
+      uint8_t* out = a.pay + f * a.pay_stride;
+      for (int k = l; k < max(nd, a.max_bytes); k += G) {
+        if (k >= nd) {
+          out[k] = 0;
+          continue;
+        }
+        uint32_t byte = 0;
+        for (int h = 0; h < 2; ++h) {
+          const int i = 2 * k + h;  // data nibble
+          // nibbles below nh: codeword 5 + i of block 0, Hamming 8/4; the others: codeword c =
+          // row `dst` of block `blk` of the remaining blocks, as in k_soft_chain_decode
+          const bool first = i < nh;
+          const int c = first ? 0 : i - nh;
+          const int blk = c / SF;
+          const int dst = c - blk * SF;
+          const float* s = first ? row : row + (size_t)(8 + blk * nbits) * SF;
+          const uint32_t wb = first ? kWhiten.v[0][i] : wh[i] & mask;
+          uint32_t diff;
+          const uint32_t nib = soft_codeword<SF>(s, first ? SF - 2 : SF, first ? 5 + i : dst, wb, first ? 4 : rdd, diff);
+          byte = (byte << 4) | nib;
+          nc += diff != 0 ? 1u : 0u;
+        }
+        if (k < n) {
+          out[k] = (uint8_t)byte;
+          if (crc) w ^= crc_term(byte, (uint32_t)(n - 1 - k), levels);
+        } else {
+          w ^= byte << (k == n ? 16 : 24);
+          if (k < a.max_bytes) out[k] = 0;
+        }
+      }
+    }
+    w = group_xor(w, a.lg);
+    nc = group_sum(nc, a.lg);
+    if (whole && crc && crc_finish(w & 0xFFFF, n) != (w >> 16)) status = LORA_FRAME_CRC;
+  }
+  if (live && l == 0) {
+    if (a.status) a.status[f] = status;
+    if (a.nbytes) a.nbytes[f] = n;
+    if (a.rdd) a.rdd[f] = rdd;
+    if (a.has_crc) a.has_crc[f] = crc;
+    if (a.nsym) a.nsym[f] = ns;
+    if (a.corrected) a.corrected[f] = (int32_t)(hcorr + nc);
+    if (a.hdr_flips) a.hdr_flips[f] = (int32_t)flips;
+  }
+}
+
 // ---------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------
@@ -1023,4 +1184,50 @@ int64_t lora_decode_frame_batch(int sf, const uint16_t* symbols, int64_t frames,
   a.errors = errors;
   a.pay = payload;
   return launch_frames(k_frame_decode, a, frames, a.lg, device, stream, max_bytes);
+}
+
+int64_t lora_decode_frame_soft_batch(int sf, const float* llr, int64_t frames, int64_t sym_count,
+                                     int64_t sym_stride, const int32_t* avail, int32_t* status, int32_t* nbytes,
+                                     int32_t* rdd, int32_t* has_crc, int32_t* nsym, int32_t* corrected,
+                                     int32_t* hdr_flips, int max_flips, uint8_t* payload, int64_t max_bytes,
+                                     int64_t payload_stride, int device, void* stream) {
+  if (sf < 7 || sf > 12) return set_last_error(LORA_EINVAL, "sf must be in 7..12");
+  if (frames < 0 || sym_count < 0 || sym_count >= (int64_t(1) << 31))
+    return set_last_error(LORA_EINVAL, "bad frames / sym_count");
+  if (sym_stride < sym_count) return set_last_error(LORA_EINVAL, "sym_stride smaller than sym_count");
+  if (max_flips < 0 || max_flips > 40) return set_last_error(LORA_EINVAL, "max_flips must be in 0..40");
+  if (!payload) max_bytes = 0;  // header-only mode
+  if (max_bytes < 0 || max_bytes > kMaxPayload) return set_last_error(LORA_EINVAL, "max_bytes must be in 0..255");
+  if (payload && payload_stride < max_bytes)
+    return set_last_error(LORA_EINVAL, "payload_stride smaller than max_bytes");
+  if (frames == 0) return max_bytes;
+  if (sym_count > 0 && !llr) return set_last_error(LORA_EINVAL, "null buffer");
+  if (!payload && !status && !nbytes && !rdd && !has_crc && !nsym && !corrected && !hdr_flips)
+    return max_bytes;  // nothing to write
+  FrameSoftArgs a{};
+  a.max_bytes = (int)max_bytes;
+  a.max_flips = max_flips;
+  a.lg = payload ? group_lg(max_bytes + 2) : 0;
+  a.cols = (int)sym_count;
+  a.frames = frames;
+  a.sym_stride = sym_stride;
+  a.pay_stride = payload_stride;
+  a.llr = llr;
+  a.avail = avail;
+  a.status = status;
+  a.nbytes = nbytes;
+  a.rdd = rdd;
+  a.has_crc = has_crc;
+  a.nsym = nsym;
+  a.corrected = corrected;
+  a.hdr_flips = hdr_flips;
+  a.pay = payload;
+  switch (sf) {
+    case 7: return launch_frames(k_frame_decode_soft<7>, a, frames, a.lg, device, stream, max_bytes);
+    case 8: return launch_frames(k_frame_decode_soft<8>, a, frames, a.lg, device, stream, max_bytes);
+    case 9: return launch_frames(k_frame_decode_soft<9>, a, frames, a.lg, device, stream, max_bytes);
+    case 10: return launch_frames(k_frame_decode_soft<10>, a, frames, a.lg, device, stream, max_bytes);
+    case 11: return launch_frames(k_frame_decode_soft<11>, a, frames, a.lg, device, stream, max_bytes);
+    default: return launch_frames(k_frame_decode_soft<12>, a, frames, a.lg, device, stream, max_bytes);
+  }
 }

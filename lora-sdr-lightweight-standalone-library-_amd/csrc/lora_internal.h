@@ -173,6 +173,11 @@ int launch_detect_metrics(const KArgs& a, const float* cfo, const float* toff, c
 // llr[(frame * llr_stride + symbol) * a.sf + bit].  a.sf is 6..12 (the caller has checked).
 int launch_soft_bits(const KArgs& a, const float* cfo, const float* toff, const float* max_amp, float* llr,
                      int64_t llr_stride, int64_t frames, hipStream_t st);
+// The same with columns red_first .. red_first + red_count - 1 of every frame read as symbols of
+// a frame's header block (k_soft_bits_frame).  a.sf is 7..12, red_count > 0 and the columns lie
+// in 0 .. a.total - 1 (the caller has checked).
+int launch_soft_bits_frame(const KArgs& a, const float* cfo, const float* toff, const float* max_amp, float* llr,
+                           int64_t llr_stride, int64_t frames, int64_t red_first, int64_t red_count, hipStream_t st);
 
 // Symbols (windows) per workgroup of the detector-metrics kernels (k_detect_metrics,
 // k_detect_scan): G * N = 4096 points (32 KiB of spectra + 16 KiB of |X|^2), at most one

@@ -1,5 +1,7 @@
 // lora_metrics.hip — per-symbol detector metrics (lora_demod_metrics_batch) and soft bits
-// (lora_demod_soft_bits_batch, k_soft_bits below: another reduction of the same spectra).
+// (lora_demod_soft_bits_batch, k_soft_bits below: another reduction of the same spectra; and
+// lora_demod_soft_bits_frame_batch, k_soft_bits_frame, whose chosen columns are read as the
+// header symbols of a self-describing frame).
 //
 // For every whole symbol of every frame the four values LoRaDetector<float>::detect returns
 // (LoRaDetector.hpp:39-74): the argmax bin, `power` (the peak in dB), `powerAvg` (everything
@@ -190,10 +192,19 @@ __device__ __forceinline__ uint32_t parity(uint32_t x) { return (uint32_t)__popc
 //      cross-lane moves, and over its waves (SF 11: 2, SF 12: 4) through R;
 //   5. llr = m1 - m0 (+0 where equal), G * SF consecutive floats per workgroup and frame.
 // LDS: the 32 KiB of spectra; the runs (17 KiB) and R (at most 3 KiB at SF 6) reuse them.
-template <int SF>
-__global__ void __launch_bounds__(kThreads)
-k_soft_bits(KArgs a, const float* __restrict__ cfo, const float* __restrict__ toff,
-            const float* __restrict__ max_amp, float* __restrict__ llr, int64_t llr_stride, int64_t work) {
+//
+// RED (lora_demod_soft_bits_frame_batch, k_soft_bits_frame): columns red_first .. red_first +
+// red_count - 1 of every frame are those of a frame's header block, whose value is
+// grayToBinary16(((k + 2) >> 2) & (2^(SF-2) - 1)).  Its bit c is bit c + 2 of
+// grayToBinary16((k + 2) mod N): in step 2 such a symbol's bin k is written where bin
+// (k + 2) mod N goes, and in step 5 slot c takes the maxima of bit c + 2 (slots SF-2 and SF-1:
+// +0).  With RED off nothing of this is compiled: that instance is k_soft_bits, unchanged in
+// its source, name, arguments and outputs.
+template <int SF, bool RED>
+__device__ __forceinline__ void soft_bits_body(const KArgs& a, const float* __restrict__ cfo,
+                                               const float* __restrict__ toff, const float* __restrict__ max_amp,
+                                               float* __restrict__ llr, int64_t llr_stride, int64_t work,
+                                               uint32_t red_first, uint32_t red_count) {
   constexpr int N = 1 << SF, G = metrics_group(SF);
   constexpr int kRun = 16, kPitch = kRun + 1;
   constexpr int TN = N / kRun;               // lanes per symbol
@@ -226,7 +237,11 @@ k_soft_bits(KArgs a, const float* __restrict__ cfo, const float* __restrict__ to
   __syncthreads();  // every spectrum is read: its storage is free
 #pragma unroll
   for (int r = 0; r < kRun; ++r) {
-    const int b = tid + r * kThreads;
+    int b = tid + r * kThreads;
+    if constexpr (RED) {  // a header symbol: bin k goes where bin (k + 2) mod N does
+      const uint32_t col = (r0 + (uint32_t)(b >> SF)) % utotal;
+      if (col - red_first < red_count) b = (b & ~(N - 1)) | ((b + 2) & (N - 1));
+    }
     Qs[b + (b >> 4)] = q[r];  // run b / 16, word b % 16
   }
   __syncthreads();
@@ -268,11 +283,17 @@ k_soft_bits(KArgs a, const float* __restrict__ cfo, const float* __restrict__ to
   for (int e = tid; e < G * SF; e += kThreads) {
     const int s = e / SF, c = e - s * SF;
     if (w0 + s >= work) break;
+    int cc = c;  // the bit whose maxima slot c takes
+    if constexpr (RED) {
+      if ((r0 + (uint32_t)s) % utotal - red_first < red_count) cc = c + 2;
+    }
     uint32_t m0 = 0, m1 = 0;
+    if (!RED || cc < SF) {
 #pragma unroll
-    for (int w = 0; w < WN; ++w) {
-      m0 = max(m0, R[((s * WN + w) * SF + c) * 2]);
-      m1 = max(m1, R[((s * WN + w) * SF + c) * 2 + 1]);
+      for (int w = 0; w < WN; ++w) {
+        m0 = max(m0, R[((s * WN + w) * SF + cc) * 2]);
+        m1 = max(m1, R[((s * WN + w) * SF + cc) * 2 + 1]);
+      }
     }
     const uint32_t loc = r0 + (uint32_t)s;
     const uint32_t fq = loc / utotal;
@@ -282,11 +303,36 @@ k_soft_bits(KArgs a, const float* __restrict__ cfo, const float* __restrict__ to
 }
 
 template <int SF>
+__global__ void __launch_bounds__(kThreads)
+k_soft_bits(KArgs a, const float* __restrict__ cfo, const float* __restrict__ toff,
+            const float* __restrict__ max_amp, float* __restrict__ llr, int64_t llr_stride, int64_t work) {
+  soft_bits_body<SF, false>(a, cfo, toff, max_amp, llr, llr_stride, work, 0u, 0u);
+}
+
+template <int SF>
+__global__ void __launch_bounds__(kThreads)
+k_soft_bits_frame(KArgs a, const float* __restrict__ cfo, const float* __restrict__ toff,
+                  const float* __restrict__ max_amp, float* __restrict__ llr, int64_t llr_stride, int64_t work,
+                  uint32_t red_first, uint32_t red_count) {
+  static_assert(SF >= 7, "the header block carries SF - 2 >= 5 bits");
+  soft_bits_body<SF, true>(a, cfo, toff, max_amp, llr, llr_stride, work, red_first, red_count);
+}
+
+template <int SF>
 void launch_soft_sf(const KArgs& a, const float* cfo, const float* toff, const float* max_amp, float* llr,
                     int64_t llr_stride, int64_t work, unsigned grid, hipStream_t st) {
   constexpr size_t lds = (size_t)metrics_group(SF) * (1 << SF) * sizeof(cf);
   hipLaunchKernelGGL(k_soft_bits<SF>, dim3(grid), dim3(kThreads), lds, st, a, cfo, toff, max_amp, llr, llr_stride,
                      work);
+}
+
+template <int SF>
+void launch_soft_frame_sf(const KArgs& a, const float* cfo, const float* toff, const float* max_amp, float* llr,
+                          int64_t llr_stride, int64_t work, unsigned grid, hipStream_t st, uint32_t red_first,
+                          uint32_t red_count) {
+  constexpr size_t lds = (size_t)metrics_group(SF) * (1 << SF) * sizeof(cf);
+  hipLaunchKernelGGL(k_soft_bits_frame<SF>, dim3(grid), dim3(kThreads), lds, st, a, cfo, toff, max_amp, llr,
+                     llr_stride, work, red_first, red_count);
 }
 
 }  // namespace
@@ -325,6 +371,30 @@ int launch_soft_bits(const KArgs& a, const float* cfo, const float* toff, const 
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("k_soft_bits: ") + hipGetErrorString(e));
+  return LORA_OK;
+}
+
+// Enqueue k_soft_bits_frame (a.sf in 7..12): columns red_first .. red_first + red_count - 1 of
+// every frame are reduced (0 <= red_first, 0 < red_count, red_first + red_count <= a.total).
+int launch_soft_bits_frame(const KArgs& a, const float* cfo, const float* toff, const float* max_amp, float* llr,
+                           int64_t llr_stride, int64_t frames, int64_t red_first, int64_t red_count, hipStream_t st) {
+  const int G = metrics_group(a.sf);
+  const int64_t work = frames * a.total;
+  const int64_t grid = (work + G - 1) / G;
+  if (grid >= (int64_t(1) << 31)) return set_last_error(LORA_EINVAL, "batch too large");
+  const unsigned g = (unsigned)grid;
+  const uint32_t rf = (uint32_t)red_first, rc = (uint32_t)red_count;
+  switch (a.sf) {
+    case 7: launch_soft_frame_sf<7>(a, cfo, toff, max_amp, llr, llr_stride, work, g, st, rf, rc); break;
+    case 8: launch_soft_frame_sf<8>(a, cfo, toff, max_amp, llr, llr_stride, work, g, st, rf, rc); break;
+    case 9: launch_soft_frame_sf<9>(a, cfo, toff, max_amp, llr, llr_stride, work, g, st, rf, rc); break;
+    case 10: launch_soft_frame_sf<10>(a, cfo, toff, max_amp, llr, llr_stride, work, g, st, rf, rc); break;
+    case 11: launch_soft_frame_sf<11>(a, cfo, toff, max_amp, llr, llr_stride, work, g, st, rf, rc); break;
+    case 12: launch_soft_frame_sf<12>(a, cfo, toff, max_amp, llr, llr_stride, work, g, st, rf, rc); break;
+    default: return set_last_error(LORA_EINVAL, "reduced soft bits need sf in 7..12");
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_last_error(LORA_EIO, std::string("k_soft_bits_frame: ") + hipGetErrorString(e));
   return LORA_OK;
 }
 

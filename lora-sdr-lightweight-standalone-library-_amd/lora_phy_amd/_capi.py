@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "lora_demod_batch",
     "lora_demod_metrics_batch",
     "lora_demod_soft_bits_batch",
+    "lora_demod_soft_bits_frame_batch",
     "lora_detect_scan_windows",
     "lora_detect_scan_batch",
     "lora_find_frames_tile",
@@ -70,6 +71,7 @@ EXPORTED_SYMBOLS = (
     "lora_frame_symbols",
     "lora_encode_frame_batch",
     "lora_decode_frame_batch",
+    "lora_decode_frame_soft_batch",
     "lora_gather_frames_batch",
     "lora_demod_profile_enable",
     "lora_demod_profile_read",
@@ -177,6 +179,9 @@ def lib() -> C.CDLL:
     L.lora_demod_soft_bits_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                              C.c_void_p]
+    L.lora_demod_soft_bits_frame_batch.restype = C.c_int64
+    L.lora_demod_soft_bits_frame_batch.argtypes = (L.lora_demod_soft_bits_batch.argtypes[:10] +
+                                                   [C.c_int64, C.c_int64, C.c_void_p])
     L.lora_detect_scan_windows.restype = C.c_int64
     L.lora_detect_scan_windows.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
     L.lora_detect_scan_batch.restype = C.c_int64
@@ -278,6 +283,10 @@ def lib() -> C.CDLL:
     L.lora_decode_frame_batch.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
+    # (llr for symbols; corrected, hdr_flips and max_flips for errors)
+    L.lora_decode_frame_soft_batch.restype = C.c_int64
+    L.lora_decode_frame_soft_batch.argtypes = (L.lora_decode_frame_batch.argtypes[:12] + [C.c_void_p, C.c_int] +
+                                               L.lora_decode_frame_batch.argtypes[12:])
     L.lora_gather_frames_batch.restype = C.c_int64
     L.lora_gather_frames_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                            C.c_void_p, C.c_int64, C.c_int, C.c_void_p]

@@ -293,7 +293,7 @@ def sweep_receive(sf: int, snr_dbs: Sequence[float], frames: int = 2000, frame_s
 def sweep_receive_frames(sf: int, snr_dbs: Sequence[float], frames: int = 1000, max_bytes: int = 16, cr=1,
                          osr: int = 1, hop: Optional[int] = None, thresh_db: float = 0.0, seed: int = 1234,
                          frames_per_row: int = 4, noise_windows: int = 0, noise_batch_samples: int = 1 << 26,
-                         sync: int = 0x12, device=None) -> List[Dict]:
+                         sync: int = 0x12, device=None, soft: bool = False, max_flips: int = 5) -> List[Dict]:
     """``sweep_receive`` for frames that state their own length: what ``stream.receive_frames_device``
     returns under ``stream.impair``, with no frame length given to it.
 
@@ -312,7 +312,10 @@ def sweep_receive_frames(sf: int, snr_dbs: Sequence[float], frames: int = 1000, 
     status is OK; ``candidates`` listed and ``candidates_dropped`` beyond the candidate capacity;
     ``windows`` scanned.  With ``noise_windows > 0`` a last record (``"noise_only": True``) has the
     candidates and the false frames over at least that many windows of noise alone.  Everything
-    runs on the device; the counts of all points come to the host in one copy at the end."""
+    runs on the device; the counts of all points come to the host in one copy at the end.
+
+    ``soft`` and ``max_flips`` go to ``receive_frames_device``: the rows and their noise do not
+    depend on them, so the same seeded rows can be received both ways.  The records carry them."""
     from . import codec, stream
 
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -364,7 +367,8 @@ def sweep_receive_frames(sf: int, snr_dbs: Sequence[float], frames: int = 1000, 
 
     for i, snr in enumerate(snr_dbs):
         stream.impair(clean, snr_db=float(snr), seed=seed, first_row=i * R, out=work)
-        counts.append(tally(stream.receive_frames_device(plan, work, S, hop, sync, thresh_db)))
+        counts.append(tally(stream.receive_frames_device(plan, work, S, hop, sync, thresh_db, soft=soft,
+                                                         max_flips=max_flips)))
     noise_counts, noise_total = [], 0
     if noise_windows > 0:
         Ln = max((S + 3) * step, min(int(noise_batch_samples), 1 << 22))
@@ -375,7 +379,7 @@ def sweep_receive_frames(sf: int, snr_dbs: Sequence[float], frames: int = 1000, 
         b = 0
         while noise_total < noise_windows:
             stream.impair(None, sigma=1.0, seed=seed + 1, first_row=b * Rn, out=buf, rows=Rn, length=Ln, device=dev)
-            got = stream.receive_frames_device(plan, buf, S, hop, sync, thresh_db)
+            got = stream.receive_frames_device(plan, buf, S, hop, sync, thresh_db, soft=soft, max_flips=max_flips)
             ok = (got.frames.status.view(Rn, -1) == codec.FRAME_OK) & got.found.valid
             noise_counts.append(torch.stack([got.found.count.sum(), ok.sum(), got.candidates.sum(),
                                              (got.candidates.to(torch.int64) - Cn).clamp_min(0).sum()]))
@@ -397,4 +401,7 @@ def sweep_receive_frames(sf: int, snr_dbs: Sequence[float], frames: int = 1000, 
                     "candidates_per_window": cands / noise_total,
                     "candidate_capacity_per_window": hop / (4 * step),
                     "false_frames_per_million_windows": false * 1e6 / noise_total})
+    if soft:
+        for rec in out:
+            rec.update(soft=True, max_flips=int(max_flips))
     return out

@@ -19,6 +19,12 @@ of the whole payload behind it.  Rows of one batch may hold frames of different 
 coding rates; a decode needs no length from its caller.  The layout is this project's own (the
 reference has the two checksums, no header), stated to the bit in include/lora_mi355x.h and
 restated in numpy in tests/frame_checker.py.  SF 7-12.
+
+``decode_header_soft`` and ``decode_frame_soft`` (lora_decode_frame_soft_batch) are the same two
+decodes on per-bit LLRs whose header columns have the reduced form
+(``DemodPlan.soft_bits(reduced=(2, 8))``): every codeword, the header's included, by maximum
+likelihood, with a bound on the header bits the decoder may overrule; restated in
+tests/frame_soft_checker.py.
 """
 from __future__ import annotations
 
@@ -237,6 +243,8 @@ class FrameResult:
     nsym: torch.Tensor               # data symbols of the whole frame
     errors: torch.Tensor             # header and data codewords whose decode flagged an error
     payload: Optional[torch.Tensor]  # [F, max_bytes] uint8, zeros beyond nbytes; None: header only
+    # the soft decoders only: header bits in which the chosen codewords differ from the LLRs' signs
+    hdr_flips: Optional[torch.Tensor] = None
 
     _FIELDS = ("status", "nbytes", "rdd", "has_crc", "nsym", "errors")
 
@@ -334,3 +342,75 @@ def decode_frame(symbols: torch.Tensor, sf: int, avail: Optional[torch.Tensor] =
     None: S each).  ``max_bytes``: the payload's width, by default ``frame_capacity(sf, S)``, the
     most a frame of S symbols can hold (a frame stating more than max_bytes is FRAME_SHORT)."""
     return _decode_frames(symbols, sf, avail, max_bytes, out, False)
+
+
+# ---------------------------------------------------------------------------------
+# The same on soft bits (lora_decode_frame_soft_batch)
+# ---------------------------------------------------------------------------------
+MAX_HDR_FLIPS = 40  # the header's five codewords of eight bits
+
+
+def _decode_frames_soft(llr, sf, avail, max_bytes, max_flips, out, header_only):
+    sf, max_flips = int(sf), int(max_flips)
+    _require_cuda(llr, "llr")
+    if llr.dtype != torch.float32:
+        raise TypeError(f"llr must be torch.float32, got {llr.dtype}")
+    squeeze = llr.dim() == 2
+    t = llr.unsqueeze(0) if squeeze else llr
+    if (t.dim() != 3 or t.shape[2] != sf or (sf > 1 and t.stride(2) != 1) or (t.shape[1] > 1 and t.stride(1) != sf)
+            or (t.shape[0] > 1 and (t.stride(0) % sf or t.stride(0) < t.shape[1] * sf))):
+        raise ValueError(f"llr must be [frames, symbols, {sf}] (or [symbols, {sf}]) with unit stride in the last "
+                         f"dimension, pitch {sf} in the one before and non-overlapping rows")
+    if not 0 <= max_flips <= MAX_HDR_FLIPS:
+        raise ValueError(f"max_flips must be in 0..{MAX_HDR_FLIPS}")
+    F, S = t.shape[0], t.shape[1]
+    dev = t.device
+    if header_only:
+        max_bytes = 0
+    elif max_bytes is None:
+        max_bytes = frame_capacity(sf, S)
+    max_bytes = int(max_bytes)
+    if not 0 <= max_bytes <= MAX_PAYLOAD:
+        raise ValueError(f"max_bytes must be in 0..{MAX_PAYLOAD}")
+    if out is None:
+        fields = {k: torch.empty(F, dtype=torch.int32, device=dev) for k in FrameResult._FIELDS}
+        pay = None if header_only else torch.empty((max_bytes,) if squeeze else (F, max_bytes), dtype=torch.uint8,
+                                                   device=dev)
+        out = FrameResult(payload=pay, hdr_flips=torch.empty(F, dtype=torch.int32, device=dev), **fields)
+    ptrs = [_per_frame(getattr(out, k), "out." + k, F, dev) for k in FrameResult._FIELDS]
+    flips = _per_frame(out.hdr_flips, "out.hdr_flips", F, dev)
+    pay_ptr, pay_stride = None, 0
+    if not header_only:
+        # (a zero-width payload still has an address of its own, as in _decode_frames)
+        pay = _out_rows(out.payload, "out.payload", torch.uint8, F, max_bytes, squeeze, dev)
+        pay_ptr, pay_stride = (pay.data_ptr() or out.status.data_ptr()), _row_stride(pay)
+    _capi.check(_capi.lib().lora_decode_frame_soft_batch(sf, _ptr(t), F, S, t.stride(0) // sf if F > 1 else S,
+                                                         _per_frame(avail, "avail", F, dev), *ptrs, flips, max_flips,
+                                                         pay_ptr, max_bytes, pay_stride, dev.index, _stream(dev)))
+    return out
+
+
+def decode_header_soft(llr: torch.Tensor, sf: int, avail: Optional[torch.Tensor] = None, max_flips: int = 5,
+                       out: Optional[FrameResult] = None) -> FrameResult:
+    """``decode_header`` on soft bits (lora_decode_frame_soft_batch, header-only mode): ``llr`` is
+    a float32 [F, S, sf] (or [S, sf]) CUDA tensor, the DATA columns of each frame with the first
+    eight in the reduced form - ``plan.soft_bits(iq, res, reduced=(2, 8))[:, 2:]``; rows may be
+    such a view.  The five header codewords are decoded by maximum likelihood; ``errors`` counts
+    those whose chosen codeword differs from the signs of their LLRs and ``hdr_flips`` the bit
+    positions in which they do.  A header that needs more than ``max_flips`` (0 .. 40) of them is
+    FRAME_HEADER, like one whose checksum or fields are wrong: the default 5 is what the hard
+    gate tolerates (one bit in each codeword), and it is what keeps noise out.  ``payload`` is
+    None."""
+    return _decode_frames_soft(llr, sf, avail, None, max_flips, out, True)
+
+
+def decode_frame_soft(llr: torch.Tensor, sf: int, avail: Optional[torch.Tensor] = None,
+                      max_bytes: Optional[int] = None, max_flips: int = 5,
+                      out: Optional[FrameResult] = None) -> FrameResult:
+    """``decode_frame`` on soft bits (lora_decode_frame_soft_batch): the header as
+    ``decode_header_soft`` reads it, then every data codeword by maximum likelihood at the header's
+    coding rate, as ``decode_chain_soft`` decodes a chain.  ``avail`` and ``max_bytes`` as
+    ``decode_frame``'s; the frame's CRC16 judges the soft decode (FRAME_CRC / FRAME_OK).
+    ``errors`` counts the header and data codewords whose chosen codeword differs from the signs
+    of their LLRs."""
+    return _decode_frames_soft(llr, sf, avail, max_bytes, max_flips, out, False)

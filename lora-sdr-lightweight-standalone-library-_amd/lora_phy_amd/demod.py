@@ -11,7 +11,7 @@ import contextlib
 import ctypes as C
 import threading
 from dataclasses import dataclass
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -281,7 +281,7 @@ class DemodPlan:
                 result.max_amp.data_ptr() if self.mode == "legacy" else None)
 
     def soft_bits(self, iq: torch.Tensor, result: Optional[DemodResult] = None,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, reduced: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         """Max-log LLRs of the sf bits of every whole symbol (lora_demod_soft_bits_batch) for
         the frames of a [F, L] (or [L]) complex64 CUDA tensor: float32 [F, total, sf], column s
         = symbol s (the sync symbols are columns 0 and 1), positive = the bit of
@@ -291,12 +291,20 @@ class DemodPlan:
         for raw ones).  ``out``: a float32 [>= F, >= total, sf] tensor, contiguous in its last
         two dimensions; the [F, total, sf] view of it that was written is returned.  One kernel
         on the current stream, nothing allocated besides the output, so the call can be captured
-        in a HIP graph."""
+        in a HIP graph.
+
+        ``reduced=(first, count)`` (lora_demod_soft_bits_frame_batch, SF 7-12): columns ``first ..
+        first + count - 1`` of every frame are symbols of a self-describing frame's header block
+        - ``(2, 8)`` after the two sync symbols.  Their first sf - 2 entries are the LLRs of the
+        bits of grayToBinary16 of the bin rounded to the nearest multiple of four, the last two
+        +0.0; ``codec.decode_frame_soft`` reads them.  ``None`` and ``(first, 0)`` are the plain
+        call."""
         iq = _check_iq(iq, self.device)
         F, L = iq.shape
         dev = self.device
         if not 6 <= self.sf <= 12:
             raise ValueError("soft bits need a plan with sf in 6..12")
+        red_first, red_count = (0, 0) if reduced is None else (int(reduced[0]), int(reduced[1]))
         if self.mode == "api":
             self.symbols_per_frame(L)  # the plan's frame-length rule
         total = L // self.step
@@ -315,9 +323,14 @@ class DemodPlan:
                                  "in its last two dimensions, with non-overlapping rows")
         llr_stride = out.stride(0) // self.sf if F > 1 else total
         stride = iq.stride(0) if F > 1 else L
-        got = _capi.check(self._lib.lora_demod_soft_bits_batch(
-            self._h, iq.data_ptr(), F, L, stride, cfo, toff, amp, out.data_ptr() if out.numel() else None,
-            llr_stride, _stream_handle(dev)))
+        if reduced is None:
+            got = _capi.check(self._lib.lora_demod_soft_bits_batch(
+                self._h, iq.data_ptr(), F, L, stride, cfo, toff, amp, out.data_ptr() if out.numel() else None,
+                llr_stride, _stream_handle(dev)))
+        else:
+            got = _capi.check(self._lib.lora_demod_soft_bits_frame_batch(
+                self._h, iq.data_ptr(), F, L, stride, cfo, toff, amp, out.data_ptr() if out.numel() else None,
+                llr_stride, red_first, red_count, _stream_handle(dev)))
         assert got == total, (got, total)
         return out[:F, :total]
 
@@ -540,18 +553,20 @@ class LoRaDemod:
 
     def work_packets_device(self, iq: torch.Tensor, max_symbols: Optional[int] = None, hop: Optional[int] = None,
                             thresh_db: float = 0.0, first=None, capacity: Optional[int] = None,
-                            cand_capacity: Optional[int] = None):
+                            cand_capacity: Optional[int] = None, soft: bool = False, max_flips: int = 5):
         """Receive self-describing frames (``LoRaMod.work_frame``) from a [L] stream or [R, L] rows
         with no frame length given (``lora_phy_amd.stream.receive_frames_device`` with this block's
         plan and sync word): each frame's header states its length, coding rate and CRC flag, and
         the header's coding rate wins over this block's ``cr``.  ``max_symbols``: the longest frame
         accepted, by default ``mtu``.  Returns the stream.StreamPackets - ``found``, ``nsym``, and
         ``frames`` with every slot's status and payload; select with ``found.valid``.  ``last``
-        keeps the DemodResult of all slots.  Nothing synchronises."""
+        keeps the DemodResult of all slots.  ``soft`` and ``max_flips``: the header probe and the
+        decode on soft bits, as ``receive_frames_device``'s.  Nothing synchronises."""
         from . import stream
 
         got = stream.receive_frames_device(self.plan, iq, self.mtu if max_symbols is None else max_symbols, hop,
-                                           self.sync, thresh_db, first, capacity, cand_capacity)
+                                           self.sync, thresh_db, first, capacity, cand_capacity, soft=soft,
+                                           max_flips=max_flips)
         self.last = got.result
         return got
 

@@ -774,6 +774,7 @@ class StreamPackets:
     result: DemodResult       # of every slot cut to (2 + max_symbols) * step, zeros after its frame
     frames: "object"          # codec.FrameResult of every slot: status, nbytes, rdd, has_crc, errors, payload
     candidates: torch.Tensor  # [R] int32: candidates listed per row (above cand_capacity: some were dropped)
+    llr: Optional[torch.Tensor] = None  # soft=True: [R * capacity, 2 + max_symbols, sf] soft bits of the slots
 
 
 def _scan_rows(metrics: DetectMetrics, what: str):
@@ -877,8 +878,9 @@ def select_frames_device(cand_starts: torch.Tensor, status: torch.Tensor, nsym: 
 
 
 def _receive_frame_rows(plan: DemodPlan, rows: torch.Tensor, max_symbols, hop, sync, thresh_db, first, capacity,
-                        cand_capacity) -> StreamPackets:
-    """The nine steps of ``receive_frames_device`` on [R, L] rows (checked by the caller)."""
+                        cand_capacity, soft: bool = False, max_flips: int = 5) -> StreamPackets:
+    """The nine steps of ``receive_frames_device`` on [R, L] rows (checked by the caller); with
+    ``soft`` the two decodes run on soft bits, columns 2 - 9 (the header's) reduced."""
     from . import codec
 
     sf, step, dev = plan.sf, plan.step, plan.device
@@ -903,7 +905,11 @@ def _receive_frame_rows(plan: DemodPlan, rows: torch.Tensor, max_symbols, hop, s
     if R * C:
         at = torch.where(cstarts >= 0, cstarts + row0, cstarts).reshape(-1)
         heads = gather_frames_device(flat, at, torch.full_like(at, head_len), head_len)
-        hdr = codec.decode_header(plan.run(heads).symbols, sf)
+        if soft:
+            hdr = codec.decode_header_soft(plan.soft_bits(heads, plan.run(heads), reduced=(2, 8))[:, 2:], sf,
+                                           max_flips=max_flips)
+        else:
+            hdr = codec.decode_header(plan.run(heads).symbols, sf)
         status, hsym = hdr.status.view(R, C), hdr.nsym.view(R, C)
     else:
         status = hsym = torch.empty((R, C), dtype=torch.int32, device=dev)
@@ -916,14 +922,21 @@ def _receive_frame_rows(plan: DemodPlan, rows: torch.Tensor, max_symbols, hop, s
         return StreamPackets(found, nsym, _no_frames(max_symbols, dev), frames, ccount)
     at = torch.where(found.starts >= 0, found.starts + row0, found.starts).reshape(-1)
     length = (nsym.reshape(-1).to(torch.int64) + 2) * step
-    res = plan.run(gather_frames_device(flat, at, length, cut))
+    slots = gather_frames_device(flat, at, length, cut)
+    res = plan.run(slots)
+    if soft:
+        llr = plan.soft_bits(slots, res, reduced=(2, 8))
+        frames = codec.decode_frame_soft(llr[:, 2:], sf, avail=nsym.reshape(-1), max_bytes=max_bytes,
+                                         max_flips=max_flips)
+        return StreamPackets(found, nsym, res, frames, ccount, llr)
     frames = codec.decode_frame(res.symbols, sf, avail=nsym.reshape(-1), max_bytes=max_bytes)
     return StreamPackets(found, nsym, res, frames, ccount)
 
 
 def receive_frames_device(plan: DemodPlan, iq: torch.Tensor, max_symbols: int, hop: Optional[int] = None,
                           sync: int = 0x12, thresh_db: float = 0.0, first: Union[None, int, torch.Tensor] = None,
-                          capacity: Optional[int] = None, cand_capacity: Optional[int] = None) -> StreamPackets:
+                          capacity: Optional[int] = None, cand_capacity: Optional[int] = None,
+                          soft: bool = False, max_flips: int = 5) -> StreamPackets:
     """Receive self-describing frames (``codec.encode_frame``, ``LoRaMod.work_frame``) of any mix
     of lengths and coding rates from a [L] stream or [R, L] rows, with no frame length given and
     without the host: nothing is read back, nothing synchronises, every shape comes from host
@@ -951,7 +964,16 @@ def receive_frames_device(plan: DemodPlan, iq: torch.Tensor, max_symbols: int, h
     a max_symbols frame]); select with ``found.valid``.  A chunked caller overlaps chunks by
     ``(2 + max_symbols) * step - 1`` samples and carries ``found.end`` exactly as with
     ``receive_device``.  Limits, inherited from the finder: bw 125 kHz, ``hop`` dividing ``step``
-    at least twice, and SF 7-12 (the header block)."""
+    at least twice, and SF 7-12 (the header block).
+
+    ``soft=True``: the same steps on soft decisions.  The header probe becomes ``plan.run``,
+    ``plan.soft_bits(..., reduced=(2, 8))`` and ``codec.decode_header_soft``; the last step
+    ``plan.run``, ``plan.soft_bits(..., reduced=(2, 8))`` over the slots and
+    ``codec.decode_frame_soft`` on columns 2 onward with ``avail = nsym``.  Candidates, selection
+    and gathers are unchanged, nothing synchronises, and ``llr`` of the result holds the slots'
+    soft bits.  ``frames.errors`` then counts corrected codewords and ``frames.hdr_flips`` the
+    header bits the decoder overruled; a header that needs more than ``max_flips`` (0 .. 40) of
+    them is refused, which is what keeps noise from passing the soft header gate."""
     if not plan.dechirp:
         raise ValueError("receive_frames_device needs a plan with dechirp=True: the finder reads dechirped peaks")
     if not isinstance(iq, torch.Tensor) or iq.dim() not in (1, 2):
@@ -959,19 +981,20 @@ def receive_frames_device(plan: DemodPlan, iq: torch.Tensor, max_symbols: int, h
     hop = plan.step // 4 if hop is None else int(hop)
     _geometry(hop, plan.sf, plan.osr, 8, sync, plan.bw)
     return _receive_frame_rows(plan, _check_iq(iq, plan.device), max_symbols, hop, sync, thresh_db, first, capacity,
-                               cand_capacity)
+                               cand_capacity, soft, max_flips)
 
 
 def receive_wideband_frames_device(plan: DemodPlan, chan: "Channelizer", iq: torch.Tensor, max_symbols: int,
                                    hop: Optional[int] = None, sync: int = 0x12, thresh_db: float = 0.0,
                                    scale: Optional[float] = None, first: Union[None, int, torch.Tensor] = None,
-                                   capacity: Optional[int] = None,
-                                   cand_capacity: Optional[int] = None) -> StreamPackets:
+                                   capacity: Optional[int] = None, cand_capacity: Optional[int] = None,
+                                   soft: bool = False, max_flips: int = 5) -> StreamPackets:
     """``receive_frames_device`` for a wideband capture: ``chan.run`` on the [L] complex64 stream
     (or the raw [L, 2] integer stream, converted with ``scale``), then the same steps over the
     [C, Wc] channel rows - row r of the result is channel r, starts are in CHANNEL samples, and
     ``first`` ([C]) and the capacities count per channel with ``row_len = Wc``.  Channels may
-    carry frames of different lengths at once.  No synchronisation."""
+    carry frames of different lengths at once.  ``soft`` and ``max_flips`` as
+    ``receive_frames_device``'s.  No synchronisation."""
     if not plan.dechirp:
         raise ValueError("receive_wideband_frames_device needs a plan with dechirp=True: the finder reads "
                          "dechirped peaks")
@@ -982,7 +1005,8 @@ def receive_wideband_frames_device(plan: DemodPlan, chan: "Channelizer", iq: tor
     hop = plan.step // 4 if hop is None else int(hop)
     _geometry(hop, plan.sf, plan.osr, 8, sync, plan.bw)
     rows = chan.run(iq, scale=scale)  # [C, Wc]
-    return _receive_frame_rows(plan, rows, max_symbols, hop, sync, thresh_db, first, capacity, cand_capacity)
+    return _receive_frame_rows(plan, rows, max_symbols, hop, sync, thresh_db, first, capacity, cand_capacity, soft,
+                               max_flips)
 
 
 def gather_frames_device(iq: torch.Tensor, at: torch.Tensor, length: torch.Tensor, cut: int,
