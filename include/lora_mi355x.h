@@ -875,6 +875,55 @@ int lora_demod_last_kernels(const lora_demod_plan* plan);
  * pipeline (three launches: frame max, estimate, demod). */
 int64_t lora_demod_spec_recomputed(lora_demod_plan* plan);
 
+/* What the pipeline's certification saw and decided in the lora_demod_batch call that just ran
+ * on `workspace` (a read-only diagnostic for tests and tools; host code only, no kernel).
+ * `plan`, `workspace`, `workspace_bytes`, `frames` and `frame_len` are that call's; the caller
+ * answers for that, the entry can only check that the plan's last call took the pipeline
+ * (LORA_KERNEL_SPEC in lora_demod_last_kernels) and that the workspace holds the layout.  It
+ * synchronises `stream` (the call's), then copies into the caller's host buffers:
+ *   fp_spec[f], fp[f]  the offsets the symbol pass used (the pre-pass estimate on unscaled
+ *                      samples) and the exact ones (LoRaDemod.cpp:79-135 on the normalised
+ *                      frame), f < frames.  LORA_MODE_API: the symbol pass runs with the exact
+ *                      offsets, both are those; LORA_MODE_RAW: there are none, both are zero.
+ *   max_slot[f]        float bits: the pre-pass's max(|I|,|Q|) over the samples outside the
+ *                      data-symbol windows that fp_spec implies ([0, 2 step), a positive t_off's
+ *                      [2 step, 2 step + t_off), the frame's tail).  API and RAW: 0 (not taken).
+ *   entries[f * total + s][2]  symbol s < total = frame_len / step of frame f: the margin
+ *                      |X1| - |X2| between the top bin and the runner-up (float bits), then for
+ *                      a data symbol its window's max(|I|,|Q|) (float bits), for a LEGACY sync
+ *                      symbol (s < 2) the speculative index.  API: entries 0 and 1 are zero
+ *                      (the estimate kernel demodulated the sync symbols exactly).
+ *   list[i][2]         the symbols the certification rejected and k_spec_fix recomputed, as
+ *                      (frame, symbol of the frame), stripe after stripe; symbol 0xFFFFFFFF is
+ *                      the frame's sync pair (LEGACY).
+ * Every pipeline (LEGACY, API, RAW) zeroes the list's counters before its certification and
+ * k_spec_fix only reads them, so the list stays readable until the workspace's next call.
+ * Returns the number of listed entries - what that call added to lora_demod_spec_recomputed.
+ * Before any use of the plan: LORA_EINVAL for a NULL plan / workspace / out ("null argument"),
+ * for frames <= 0 or frame_len < 0, for a NULL buffer in `out`; LORA_ERANGE for frame_cap <
+ * frames.  Then LORA_EINVAL when the plan's last call did not take the pipeline, LORA_ERANGE
+ * for sym_cap < frames * total, for a workspace smaller than lora_demod_workspace_bytes, and -
+ * after the counters were read - for list_cap below the list's length; LORA_EIO for a HIP
+ * error or a counter beyond the list's capacity (not this call's workspace). */
+typedef struct lora_spec_frame {
+  float cfo, time_offset; /* the frame's outputs */
+  float rate;             /* rotation per sample, -2 pi cfo / N */
+  float scale;            /* 1 / max when scaled, else 1 */
+  int32_t t_off;          /* round(time_offset) */
+  int32_t scaled;         /* the frame's maximum exceeds 1 */
+  int32_t reserved[2];
+} lora_spec_frame;
+typedef struct lora_spec_trace_out {
+  lora_spec_frame* fp_spec; /* [frame_cap] */
+  lora_spec_frame* fp;      /* [frame_cap] */
+  uint32_t* max_slot;       /* [frame_cap] */
+  uint32_t* entries;        /* [sym_cap][2] */
+  uint32_t* list;           /* [list_cap][2] */
+  int64_t frame_cap, sym_cap, list_cap;
+} lora_spec_trace_out;
+int64_t lora_demod_spec_trace(const lora_demod_plan* plan, const void* workspace, size_t workspace_bytes,
+                              int64_t frames, int64_t frame_len, const lora_spec_trace_out* out, void* stream);
+
 /* Choose the plan's path explicitly (instead of the process-wide LORA_MI355X_SPEC read at
  * plan creation): speculative = 1 runs the speculative single-read pipeline wherever it
  * covers the configuration (the default), 0 always the three-launch exact path.  Both give

@@ -1374,6 +1374,73 @@ int64_t lora_demod_spec_recomputed(lora_demod_plan* plan) {
   return (int64_t)v;
 }
 
+// The certification's inputs and verdicts of the call that just ran on `workspace`, copied to
+// the host (include/lora_mi355x.h).  How the three pipelines leave the reject list: LEGACY's
+// pre-pass (k_est_split / k_est_fast<SPEC = 1>) zeroes the 16 counters; API and RAW have no
+// pre-pass and k_spec_demod<SPM != 0> zeroes them (RAW starts at that stage); the
+// certification kernels append; k_spec_fix only reads counters and list.  So after the call
+// all three hold the complete list.  API's symbol pass runs with fp_spec aliased to fp and
+// RAW's with none: the workspace's fp_spec region, like both modes' maximum slot and API's
+// sync entries, is not written and is reported as fp / zero.
+int64_t lora_demod_spec_trace(const lora_demod_plan* plan, const void* workspace, size_t workspace_bytes,
+                              int64_t frames, int64_t frame_len, const lora_spec_trace_out* out, void* stream) {
+  static_assert(sizeof(lora_spec_frame) == sizeof(lora::FrameParams), "lora_spec_frame mirrors FrameParams");
+  if (!plan || !workspace || !out) return set_error(LORA_EINVAL, "null argument");
+  if (frames <= 0 || frame_len < 0) return set_error(LORA_EINVAL, "bad frames / frame_len");
+  if (!out->fp_spec || !out->fp || !out->max_slot || !out->entries || !out->list)
+    return set_error(LORA_EINVAL, "null output buffer");
+  if (out->frame_cap < frames) return set_error(LORA_ERANGE, "frame capacity too small");
+  if (!(plan->last_kernels & LORA_KERNEL_SPEC))
+    return set_error(LORA_EINVAL, "the plan's last call did not take the speculative pipeline");
+  const int64_t total = frame_len / plan->step;
+  if (out->sym_cap < frames * total) return set_error(LORA_ERANGE, "symbol capacity too small");
+  const WsLayout wl = ws_layout(frames, frame_len, plan->step, plan->N);
+  if (workspace_bytes < wl.total) return set_error(LORA_ERANGE, "workspace too small");
+  const int mode = plan->prm.mode;
+  lora::DeviceGuard guard(plan->prm.device);
+  if (guard.err != hipSuccess) return lora::hip_error("spec trace device", guard.err);
+  HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+  const unsigned char* wsb = static_cast<const unsigned char*>(workspace);
+  // the 16 counters, 64 bytes apart
+  unsigned int counts[16 * lora::kFixStripes];
+  HIP_TRY(hipMemcpy(counts, wsb + wl.fix, sizeof(counts), hipMemcpyDeviceToHost));
+  int64_t listed = 0;
+  for (int t = 0; t < lora::kFixStripes; ++t) {
+    if ((int64_t)counts[16 * t] > wl.fix_cap)
+      return set_error(LORA_EIO, "reject list counter beyond the list's capacity");
+    listed += counts[16 * t];
+  }
+  if (out->list_cap < listed) return set_error(LORA_ERANGE, "list capacity too small");
+  const size_t fbytes = (size_t)frames * sizeof(lora_spec_frame);
+  HIP_TRY(hipMemcpy(out->fp, wsb + wl.fp, fbytes, hipMemcpyDeviceToHost));
+  if (mode == LORA_MODE_LEGACY) {
+    HIP_TRY(hipMemcpy(out->fp_spec, wsb + wl.fp_spec, fbytes, hipMemcpyDeviceToHost));
+    // (one slot per frame: the pipeline runs with mx_bpf = 1)
+    HIP_TRY(hipMemcpy(out->max_slot, wsb, (size_t)frames * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  } else {
+    std::memcpy(out->fp_spec, out->fp, fbytes);
+    std::memset(out->max_slot, 0, (size_t)frames * sizeof(uint32_t));
+  }
+  if (frames * total > 0)
+    HIP_TRY(hipMemcpy(out->entries, wsb + wl.marg, (size_t)(frames * total) * 2 * sizeof(uint32_t),
+                      hipMemcpyDeviceToHost));
+  if (mode == LORA_MODE_API && total >= 2)
+    for (int64_t f = 0; f < frames; ++f) std::memset(out->entries + 2 * f * total, 0, 4 * sizeof(uint32_t));
+  const unsigned char* lists = wsb + wl.fix + 64 * lora::kFixStripes;
+  uint32_t* dst = out->list;
+  for (int t = 0; t < lora::kFixStripes; ++t) {
+    const size_t n = counts[16 * t];
+    if (n) HIP_TRY(hipMemcpy(dst, lists + 2 * sizeof(uint32_t) * (size_t)t * (size_t)wl.fix_cap, n * 2 * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost));
+    // the kernels list data symbol j of LEGACY / API frames: symbol 2 + j of the frame
+    if (mode != LORA_MODE_RAW)
+      for (size_t i = 0; i < n; ++i)
+        if (dst[2 * i + 1] != 0xFFFFFFFFu) dst[2 * i + 1] += 2;
+    dst += 2 * n;
+  }
+  return listed;
+}
+
 int64_t lora_demod_batch(lora_demod_plan* plan, const float* iq, int64_t frames, int64_t frame_len,
                          int64_t frame_stride, const lora_demod_outputs* out, void* workspace,
                          size_t workspace_bytes, void* stream) {

@@ -11,11 +11,12 @@ transmit (the synthesis bank) are in :mod:`lora_phy_amd.stream`.
 """
 from . import _capi, codec, codes, iq_io, phy, shard, stream  # noqa: F401
 from ._capi import LoraError
-from .demod import DemodPlan, DemodResult, DetectMetrics, LoRaDemod, compensate_offsets, spec_pipeline
+from .demod import (DemodPlan, DemodResult, DetectMetrics, LoRaDemod, SpecTrace, compensate_offsets,
+                    spec_pipeline)
 from .mod import LoRaMod, modulate
 from .stream import cfo_word, impair, noise_sigma
 
-__all__ = ["DemodPlan", "DemodResult", "DetectMetrics", "LoRaDemod", "LoRaMod", "LoraError", "modulate",
+__all__ = ["DemodPlan", "DemodResult", "DetectMetrics", "SpecTrace", "LoRaDemod", "LoRaMod", "LoraError", "modulate",
            "compensate_offsets", "spec_pipeline", "codec", "codes", "iq_io", "phy", "shard", "stream", "lib_path", "version", "source_hash",
            "check_build", "impair", "cfo_word", "noise_sigma"]
 

@@ -77,6 +77,7 @@ EXPORTED_SYMBOLS = (
     "lora_demod_profile_read",
     "lora_demod_last_kernels",
     "lora_demod_spec_recomputed",
+    "lora_demod_spec_trace",
     "lora_demod_plan_set_pipeline",
     "lora_aql_last_profile",
     "lora_last_error",
@@ -117,6 +118,21 @@ class SymbolMetrics(C.Structure):
         ("f_index", C.c_void_p),
         ("index", C.c_void_p),
         ("stride", C.c_int64),
+    ]
+
+
+class SpecTraceOut(C.Structure):
+    """lora_spec_trace_out: the caller's host buffers of lora_demod_spec_trace."""
+
+    _fields_ = [
+        ("fp_spec", C.c_void_p),
+        ("fp", C.c_void_p),
+        ("max_slot", C.c_void_p),
+        ("entries", C.c_void_p),
+        ("list", C.c_void_p),
+        ("frame_cap", C.c_int64),
+        ("sym_cap", C.c_int64),
+        ("list_cap", C.c_int64),
     ]
 
 
@@ -298,6 +314,9 @@ def lib() -> C.CDLL:
     L.lora_demod_last_kernels.argtypes = [C.c_void_p]
     L.lora_demod_spec_recomputed.restype = C.c_int64
     L.lora_demod_spec_recomputed.argtypes = [C.c_void_p]
+    L.lora_demod_spec_trace.restype = C.c_int64
+    L.lora_demod_spec_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64,
+                                        C.POINTER(SpecTraceOut), C.c_void_p]
     L.lora_demod_plan_set_pipeline.restype = C.c_int
     L.lora_demod_plan_set_pipeline.argtypes = [C.c_void_p, C.c_int]
     L.lora_aql_last_profile.restype = C.c_int

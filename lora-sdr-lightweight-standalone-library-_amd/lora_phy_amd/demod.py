@@ -62,6 +62,24 @@ class DetectMetrics:
         return self.snr_db[:, first:].double().mean(dim=1).float()
 
 
+# lora_spec_frame (include/lora_mi355x.h) as a numpy record
+SPEC_FRAME_DTYPE = [("cfo", "<f4"), ("time_offset", "<f4"), ("rate", "<f4"), ("scale", "<f4"),
+                    ("t_off", "<i4"), ("scaled", "<i4"), ("reserved", "<i4", (2,))]
+
+
+@dataclass
+class SpecTrace:
+    """``DemodPlan.spec_trace()``: the certification's inputs and verdicts of the last ``run``
+    (lora_demod_spec_trace in include/lora_mi355x.h defines every field), host numpy arrays."""
+
+    fp_spec: object   # [F] SPEC_FRAME_DTYPE  the offsets the symbol pass used
+    fp: object        # [F] SPEC_FRAME_DTYPE  the exact offsets
+    max_slot: object  # [F] uint32            float bits: the maximum outside the data windows
+    margin: object    # [F, total] float32    |X1| - |X2| per symbol of the frame
+    aux: object       # [F, total] uint32     data symbol: the window maximum's float bits; sync: the index
+    rejected: object  # [K, 2] uint32         (frame, symbol of the frame | 0xFFFFFFFF = the sync pair)
+
+
 def _stream_handle(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -239,9 +257,35 @@ class DemodPlan:
                                out.sync.data_ptr(), out.cfo.data_ptr(), out.time_offset.data_ptr(),
                                out.max_amp.data_ptr())
         stride = iq.stride(0) if F > 1 else L
+        st = _stream_handle(dev)
         _capi.check(self._lib.lora_demod_batch(self._h, iq.data_ptr(), F, L, stride, C.byref(o),
-                                               ws.data_ptr(), ws.numel(), _stream_handle(dev)))
+                                               ws.data_ptr(), ws.numel(), st))
+        self._last_run = (F, L, ws, st)  # what spec_trace() reads back
         return out
+
+    def spec_trace(self) -> SpecTrace:
+        """What the speculative pipeline's certification saw and decided in the last ``run``
+        (lora_demod_spec_trace), as numpy arrays on the host: a diagnostic for tests and tools.
+        Synchronises the run's stream.  Raises when no ``run`` took the pipeline last."""
+        import numpy as np
+
+        last = getattr(self, "_last_run", None)
+        if last is None:
+            raise RuntimeError("run() has not run")
+        F, L, ws, stream = last
+        total = L // self.step
+        fp_spec = np.zeros(F, SPEC_FRAME_DTYPE)
+        fp = np.zeros(F, SPEC_FRAME_DTYPE)
+        max_slot = np.zeros(F, np.uint32)
+        entries = np.zeros((F, total, 2), np.uint32)
+        # the most the certification can list: every symbol, and a sync pair per frame
+        rejected = np.zeros((F * (total + 1), 2), np.uint32)
+        o = _capi.SpecTraceOut(fp_spec.ctypes.data, fp.ctypes.data, max_slot.ctypes.data, entries.ctypes.data,
+                               rejected.ctypes.data, F, F * total, len(rejected))
+        n = _capi.check(self._lib.lora_demod_spec_trace(self._h, ws.data_ptr(), ws.numel(), F, L, C.byref(o),
+                                                        stream))
+        return SpecTrace(fp_spec, fp, max_slot, entries[:, :, 0].copy().view(np.float32), entries[:, :, 1].copy(),
+                         rejected[:n].copy())
 
     def detect_metrics(self, iq: torch.Tensor, result: Optional[DemodResult] = None,
                        out: Optional[DetectMetrics] = None) -> DetectMetrics:
