@@ -351,6 +351,115 @@ int64_t lora_select_frames_batch(const int64_t* cand_starts, const int32_t* stat
                                  int64_t max_symbols, int64_t capacity, int64_t* starts, int32_t* out_nsym,
                                  int32_t* count, int64_t* end, int device, void* stream);
 
+/* Preambled frames: a preamble and a start-of-frame delimiter (SFD) in front of the frame, so
+ * that a receiver can sum spectra over symbols and tell a carrier offset from a timing offset.
+ * The layout is the library's own (no interoperability with a radio is claimed).  With N = 2^sf,
+ * step = N*osr and genChirp as ChirpGenerator.hpp:23-50, a preambled frame of P preamble
+ * symbols and S data symbols is four parts, each from its own genChirp chain that starts at
+ * phase 0, with the amplitude clamped to [-1, 1] as lora_mod_batch clamps it (LoRaMod.cpp:16):
+ *   pre    P up-chirps genChirp(f0 = 0, NN = step, down = false), phase carried from one to the
+ *          next; P is 4..64;
+ *   sync   the two sync symbols exactly as lora_mod_batch emits them: samples [0, 2*step) of its
+ *          frame;
+ *   sfd    two down-chirps genChirp(f0 = 0, NN = step, down = true) and a quarter of one
+ *          (NN = step/4), phase carried;
+ *   data   the data symbols exactly as lora_mod_batch emits them: samples [2*step, (2+S)*step)
+ *          of the same frame.
+ * The length is (P + 2 + S)*step + tail, tail = 9*step/4.  The phase is NOT continuous across the
+ * three joins, on purpose: a receiver that gathers [sync | data] has lora_mod_batch's frame bit
+ * for bit, so every bit-exact contract of the demodulator, the header and the CRC carries over,
+ * and the receiver is non-coherent across symbols anyway.  (A phase-continuous modulator kernel
+ * is not provided.)  "start" of a preambled frame is the sample of its first sync symbol, as
+ * everywhere else.
+ *
+ * lora_preamble_tables: host arithmetic only (no HIP call): writes pre (P*step complex samples,
+ * 2 floats each) and sfd (tail samples) into host buffers; either may be NULL.  Returns P*step.
+ * LORA_EINVAL: sf outside 2..12, a bad bw_hz, preamble outside 4..64, step not a multiple of 4.
+ * osr 0 is taken as 1. */
+int64_t lora_preamble_tables(unsigned sf, unsigned osr, unsigned bw_hz, float amplitude, int64_t preamble,
+                             float* pre, float* sfd);
+
+/* The accumulating scan: lora_detect_scan_batch's spectra summed over `acc` consecutive symbols.
+ * W is lora_detect_scan_windows' count and k = step / hop.  acc is 1..8; with acc > 1 hop must
+ * divide step.  Wa = W - (acc-1)*k when that is positive, else 0.  Window w of the plain scan
+ * has the spectrum P_w[b] = re*re + im*im of lora_detect_scan_batch's FFT (same loads, dechirp
+ * product, window and transform, no contraction); with conj != 0 every sample is conjugated
+ * before the dechirp product, so the entry equals the scan of the conjugated stream (a
+ * down-chirp then dechirps like an up-chirp).  The summed spectrum is
+ *   S_w[b] = (((P_w[b] + P_{w+k}[b]) + P_{w+2k}[b]) + ...)   acc terms, fp32, in this order,
+ * one rounding per addition, summed afresh for every w.  For w < Wa:
+ *   index      the lowest-index maximum of S_w, strict '>' from 0 (LoRaDetector.hpp:53-57);
+ *   power      20*log10f(sqrtf(maxv)) - power_scale, maxv the maximum (LoRaDetector.hpp:61,64);
+ *   power_avg  20*log10f(sqrtf((float)(total - maxv))) - power_scale, total the double sum of S_w
+ *              in bin order (LoRaDetector.hpp:39-74's statements on S_w).
+ * There is no f_index.  acc == 1 with conj == 0 equals lora_detect_scan_batch bit for bit.  The
+ * kernel recomputes the acc spectra of every output window (acc times the plain scan's work).
+ * Outputs are [rows][out_stride] with column w; any of the three may be NULL.
+ *
+ * lora_detect_scan_acc_windows: host arithmetic only; Wa.
+ * lora_detect_scan_acc_batch: one kernel on `stream`, nothing allocated or synchronised, columns
+ * 0 .. Wa-1 of every output given fully written and nothing beyond.  rows == 0, Wa == 0 or no
+ * output: no launch.  LORA_EINVAL before any HIP call: lora_detect_scan_batch's cases, acc
+ * outside 1..8, acc > 1 with hop not dividing step, out_stride < Wa with an output given.
+ * Returns Wa. */
+int64_t lora_detect_scan_acc_windows(const lora_demod_plan* plan, int64_t row_len, int64_t hop, int64_t acc);
+int64_t lora_detect_scan_acc_batch(lora_demod_plan* plan, const float* iq, int64_t rows, int64_t row_len,
+                                   int64_t row_stride, int64_t hop, int64_t acc, int conj, float* power,
+                                   float* power_avg, uint16_t* index, int64_t out_stride, void* stream);
+
+/* The preamble finder: frame starts and integer carrier offsets from two accumulating scans of
+ * the same rows with the same hop by a dechirping plan at bw 125 kHz: up_* with acc = m =
+ * params.acc_up and conj = 0 (Wu windows), dn_* with acc = 2 and conj = 1 (Wd windows).  A
+ * window d chips late under an offset of c bins sees bin d + c on the up side and d - c on the
+ * down side, which is what separates the two.  With N = 2^sf, step = N*osr, k = step / hop >= 4,
+ * tail = 9*step/4: for down window w with (2+m)*k <= w, w + k < Wd and u = w - (2+m)*k < Wu, all
+ * of these must hold:
+ *   1. dn_power[w] - dn_avg[w] >= thresh_dn_db and up_power[u] - up_avg[u] >= thresh_up_db (one
+ *      fp32 subtraction each; NaN fails, +inf passes);
+ *   2. dn_power[w] >= dn_power[w-k] and dn_power[w] > dn_power[w+k]: the symbol where both summed
+ *      windows lie on down-chirps;
+ *   3. s = (up_index[u] + dn_index[w]) mod N, minus N when s >= N/2; d = floor(s / 2);
+ *      c = (up_index[u] - d) mod N, minus N when c >= N/2; |c| <= max_cfo_bins - which rejects the
+ *      (d +- N/2, c +- N/2) alias that windows near a quarter symbol off produce;
+ *   4. start = w*hop - d*osr - 2*step, the first sync symbol, with start >= 0 and
+ *      start + 10*step + tail <= row_len.
+ * A candidate is listed in increasing w, unless its (start, c) pair equals that of the previous
+ * window that passed 1-4, listed or not.  Per row: count (may exceed capacity), starts and
+ * cfo_bins [rows][capacity], -1 and 0 in the empty slots.
+ * One kernel on `stream` of params.device, one workgroup per row, nothing allocated or
+ * synchronised, every output fully written; rows == 0: no launch.  LORA_EINVAL before any HIP
+ * call: a NULL params or count, NULL starts or cfo_bins with capacity > 0, NULL metrics with
+ * windows to test, sf outside 7..12, osr outside 1..65536, hop not dividing step or k < 4,
+ * acc_up outside 2..8, max_cfo_bins outside 0 .. N/4 - 1, negative sizes, a stride below its
+ * window count with more than one row, Wu or Wd >= 2^31, rows >= 2^31.  Returns rows. */
+typedef struct {
+  unsigned sf;
+  unsigned osr;
+  int64_t hop;
+  int acc_up;
+  float thresh_up_db;
+  float thresh_dn_db;
+  int max_cfo_bins;
+  int device;
+} lora_preamble_params;
+int64_t lora_find_preamble_batch(const lora_preamble_params* params, const float* up_power, const float* up_avg,
+                                 const uint16_t* up_index, int64_t Wu, int64_t up_stride, const float* dn_power,
+                                 const float* dn_avg, const uint16_t* dn_index, int64_t Wd, int64_t dn_stride,
+                                 int64_t rows, int64_t row_len, int64_t capacity, int64_t* starts,
+                                 int32_t* cfo_bins, int32_t* count, void* stream);
+
+/* lora_select_frames_batch's pass for preambled frames, by the same kernel: a frame ends at
+ * start + (2 + nsym)*step + tail (the slot is accepted when that is <= row_len, and first becomes
+ * it), and one int32 per slot, cand_word [rows][slots], is carried to the accepted slot's
+ * out_word [rows][capacity] (0 in the empty slots); cand_word and out_word may both be NULL.
+ * tail == 0 without words is lora_select_frames_batch.  LORA_EINVAL as that entry's, and for
+ * tail < 0 or only one of cand_word (with slots > 0) and out_word (with capacity > 0) given. */
+int64_t lora_select_preamble_batch(const int64_t* cand_starts, const int32_t* cand_word, const int32_t* status,
+                                   const int32_t* nsym, int64_t rows, int64_t slots, const int64_t* first,
+                                   int64_t row_len, int64_t step, int64_t tail, int64_t max_symbols,
+                                   int64_t capacity, int64_t* starts, int32_t* out_word, int32_t* out_nsym,
+                                   int32_t* count, int64_t* end, int device, void* stream);
+
 /* Digital down-converter bank: one wideband stream in, `channels` streams at the demodulator's
  * rate out, from one read of the wideband data.  The reference has no channelizer; this
  * definition is the library's own (like the finder's rule and the soft bits).

@@ -1898,6 +1898,73 @@ int64_t lora_detect_scan_batch(lora_demod_plan* plan, const float* iq, int64_t r
   return rc < 0 ? rc : W;
 }
 
+int64_t lora_detect_scan_acc_windows(const lora_demod_plan* plan, int64_t row_len, int64_t hop, int64_t acc) {
+  if (acc < 1 || acc > 8) return set_error(LORA_EINVAL, "acc must be in 1..8");
+  if (!plan) return set_error(LORA_EINVAL, "null plan");
+  if (row_len < 0 || hop < 1) return set_error(LORA_EINVAL, "row_len must be >= 0 and hop >= 1");
+  if (acc > 1 && plan->step % hop != 0) return set_error(LORA_EINVAL, "with acc > 1, hop must divide step");
+  return lora::scan_acc_windows(row_len, plan->step, hop, acc);
+}
+
+int64_t lora_detect_scan_acc_batch(lora_demod_plan* plan, const float* iq, int64_t rows, int64_t row_len,
+                                   int64_t row_stride, int64_t hop, int64_t acc, int conj, float* power,
+                                   float* power_avg, uint16_t* index, int64_t out_stride, void* stream) {
+  // (the checks that need no plan come first, so that they can be seen without a GPU)
+  if (acc < 1 || acc > 8) return set_error(LORA_EINVAL, "acc must be in 1..8");
+  if (rows < 0 || row_len < 0 || row_stride < 0 || out_stride < 0)
+    return set_error(LORA_EINVAL, "negative rows / row_len / row_stride / out_stride");
+  if (hop < 1) return set_error(LORA_EINVAL, "hop must be >= 1");
+  if (!plan) return set_error(LORA_EINVAL, "null argument");
+  if (acc > 1 && plan->step % hop != 0) return set_error(LORA_EINVAL, "with acc > 1, hop must divide step");
+  if (row_len >= (int64_t(1) << 31)) return set_error(LORA_EINVAL, "row_len must be < 2^31");
+  if (rows > 1 && row_stride < row_len) return set_error(LORA_EINVAL, "row_stride smaller than row_len");
+  const int64_t Wa = lora::scan_acc_windows(row_len, plan->step, hop, acc);
+  const bool any = power || power_avg || index;
+  if (any && out_stride < Wa) return set_error(LORA_EINVAL, "out_stride smaller than windows per row");
+  const lora_demod_params& p = plan->prm;
+  const int64_t grid = lora::scan_grid((int)p.sf, Wa, rows);
+  if (grid < 0) return set_error(LORA_EINVAL, "batch too large");
+  if (grid > 0 && !iq) return set_error(LORA_EINVAL, "null iq");
+  if (grid == 0 || !any) return Wa;
+  lora::DeviceGuard guard(p.device);
+  if (guard.err != hipSuccess) return lora::hip_error("scan device", guard.err);
+  KArgs a = plan_kargs(plan, iq, row_len, row_stride);
+  a.mode = LORA_MODE_RAW;
+  a.dechirp = p.dechirp ? 1 : 0;
+  const int rc = lora::launch_detect_scan_acc(a, rows, hop, (int)acc, conj ? 1 : 0, power, power_avg, index,
+                                              out_stride, static_cast<hipStream_t>(stream));
+  return rc < 0 ? rc : Wa;
+}
+
+int64_t lora_preamble_tables(unsigned sf, unsigned osr, unsigned bw_hz, float amplitude, int64_t preamble,
+                             float* pre, float* sfd) {
+  if (sf < 2 || sf > 12) return set_error(LORA_EINVAL, "sf must be in 2..12");
+  if (osr == 0) osr = 1;
+  if (!bw_ok(bw_hz)) return set_error(LORA_EINVAL, "bad bw_hz");
+  if (preamble < 4 || preamble > 64) return set_error(LORA_EINVAL, "preamble must be in 4..64");
+  const int N = 1 << sf;
+  const int64_t step64 = (int64_t)N * osr;
+  if (step64 % 4 != 0 || step64 >= (int64_t(1) << 27))
+    return set_error(LORA_EINVAL, "step = N * osr must be a multiple of 4 below 2^27");
+  const int step = (int)step64;
+  const float bws = bw_scale_of(bw_hz);
+  const float ampl = std::max(-1.0f, std::min(1.0f, amplitude));  // LoRaMod.cpp:16
+  if (pre) {
+    float ph = 0.0f;
+    for (int64_t s = 0; s < preamble; ++s)
+      host_gen_chirp(reinterpret_cast<std::complex<float>*>(pre) + s * step, N, (int)osr, step, 0.0f, false, ampl, ph,
+                     bws);
+  }
+  if (sfd) {
+    float ph = 0.0f;
+    std::complex<float>* o = reinterpret_cast<std::complex<float>*>(sfd);
+    host_gen_chirp(o, N, (int)osr, step, 0.0f, true, ampl, ph, bws);
+    host_gen_chirp(o + step, N, (int)osr, step, 0.0f, true, ampl, ph, bws);
+    host_gen_chirp(o + 2 * step, N, (int)osr, step / 4, 0.0f, true, ampl, ph, bws);
+  }
+  return preamble * step64;
+}
+
 int64_t lora_compensate_offsets_batch(unsigned sf, unsigned osr, const float* in, int64_t frames,
                                       int64_t frame_len, int64_t frame_stride, const float* cfo,
                                       const float* time_offset, int device, void* stream,

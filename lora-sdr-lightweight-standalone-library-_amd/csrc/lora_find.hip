@@ -368,6 +368,11 @@ struct SelectArgs {
   int32_t* out_nsym;       // [rows][capacity]
   int32_t* count;          // [rows]
   int64_t* end;            // [rows]
+  // lora_select_preamble_batch: samples a frame takes beyond its (2 + nsym) symbols, and one
+  // word per slot carried to the accepted slot (both null: none)
+  int64_t tail;
+  const int32_t* word;     // [rows][slots] or null
+  int32_t* out_word;       // [rows][capacity] or null
 };
 
 __global__ void __launch_bounds__(kSelThreads) k_select_frames(SelectArgs a) {
@@ -379,20 +384,29 @@ __global__ void __launch_bounds__(kSelThreads) k_select_frames(SelectArgs a) {
   const int64_t row = blockIdx.x;
   int64_t* out_starts = a.out_starts + row * a.capacity;
   int32_t* out_nsym = a.out_nsym + row * a.capacity;
+  int32_t* out_word = a.out_word ? a.out_word + row * a.capacity : nullptr;
   if (tid == 0) {
     s_first = a.first ? a.first[row] : 0;
     s_cnt = 0;
   }
+  // With a word to carry, the serial lane leaves in ns[i] of every slot it stores, in place of
+  // the nsym it has used, -1 - (the slot's output position - cnt0), cnt0 the count before this
+  // turn; after the turn's barrier lane i, which holds slot i's word, stores it there.  (No LDS
+  // beyond the pass's own; an eligible slot's nsym is never negative.  A turn stores at most
+  // kSelThreads slots, so the mark lies in -kSelThreads .. -1 and the position it stands for in
+  // cnt0 .. cnt0 + kSelThreads - 1, below capacity because only stored slots are marked.)
+  int64_t cnt0 = 0;
   for (int64_t base = 0; base < a.slots; base += kSelThreads) {
     const int64_t j = base + tid;
     bool el = false;
     int64_t s = -1;
-    int32_t n = 0;
+    int32_t n = 0, wv = 0;
     if (j < a.slots) {
       s = a.starts[row * a.slots + j];
       n = a.nsym[row * a.slots + j];
+      if (a.word) wv = a.word[row * a.slots + j];
       el = a.status[row * a.slots + j] == LORA_FRAME_OK && n >= 0 && n <= a.max_symbols && s >= 0 &&
-           s <= a.row_len - (2 + (int64_t)n) * a.step;
+           s <= a.row_len - (2 + (int64_t)n) * a.step - a.tail;
     }
     const unsigned long long m = __ballot(el);
     st[tid] = s;
@@ -405,18 +419,24 @@ __global__ void __launch_bounds__(kSelThreads) k_select_frames(SelectArgs a) {
         for (unsigned long long b = elig[v]; b != 0ull; b &= b - 1) {
           const int i = v * 64 + __ffsll((long long)b) - 1;
           if (st[i] < first) continue;
+          const int32_t ni = ns[i];
           if (cnt < a.capacity) {
             out_starts[cnt] = st[i];
-            out_nsym[cnt] = ns[i];
+            out_nsym[cnt] = ni;
+            if (out_word) ns[i] = -1 - (int32_t)(cnt - s_cnt);
           }
           ++cnt;
-          first = st[i] + (2 + (int64_t)ns[i]) * a.step;
+          first = st[i] + (2 + (int64_t)ni) * a.step + a.tail;
         }
       }
       s_first = first;
       s_cnt = cnt;
     }
     __syncthreads();
+    if (out_word) {
+      if (el && ns[tid] < 0) out_word[cnt0 + (-1 - ns[tid])] = wv;
+      cnt0 = s_cnt;  // (rewritten by lane 0 only after the next turn's first barrier)
+    }
   }
   __syncthreads();  // (no slots: s_first and s_cnt as tid 0 set them)
   const int64_t done = s_cnt;
@@ -427,6 +447,119 @@ __global__ void __launch_bounds__(kSelThreads) k_select_frames(SelectArgs a) {
   for (int64_t i = (done < a.capacity ? done : a.capacity) + tid; i < a.capacity; i += kSelThreads) {
     out_starts[i] = -1;
     out_nsym[i] = 0;
+    if (out_word) out_word[i] = 0;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Preambled frames: lora_find_preamble_batch.  The rule (include/lora_mi355x.h) reads the up scan
+// at u = w - (2 + m) * k and the down scan at w - k, w and w + k, so like the candidate list it
+// is parallel over w but for the local "differs from the previous passing pair" test: the
+// geometry, ballots and prefix count are k_find_candidates'.
+// ---------------------------------------------------------------------------------------------
+struct PreambleArgs {
+  const float *up_power, *up_avg, *dn_power, *dn_avg;
+  const uint16_t *up_index, *dn_index;
+  int64_t up_stride, dn_stride;
+  int64_t w_lo, w_hi;  // down windows w_lo <= w < w_hi are tested (w_hi <= w_lo: none)
+  int64_t lag;         // (2 + m) * k
+  int64_t hop, osr, two_step, capacity;
+  int64_t last_start;  // row_len - 10 * step - tail (may be < 0)
+  int64_t* starts;     // [rows][capacity]
+  int32_t* cfo;        // [rows][capacity]
+  int32_t* count;      // [rows]
+  int k, N, max_cfo;
+  float thresh_up, thresh_dn;
+};
+
+__global__ void __launch_bounds__(kThreads) k_find_preamble(PreambleArgs a) {
+  __shared__ unsigned long long elig[kWaves], listed[kWaves];
+  __shared__ int64_t st[kThreads];
+  __shared__ int32_t cf_[kThreads];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t row = blockIdx.x;
+  const float* up = a.up_power + row * a.up_stride;
+  const float* ua = a.up_avg + row * a.up_stride;
+  const uint16_t* ui = a.up_index + row * a.up_stride;
+  const float* dp = a.dn_power + row * a.dn_stride;
+  const float* da = a.dn_avg + row * a.dn_stride;
+  const uint16_t* di = a.dn_index + row * a.dn_stride;
+  int64_t* starts = a.starts + row * a.capacity;
+  int32_t* cfo = a.cfo + row * a.capacity;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int64_t cnt = 0, prev_s = -1;  // (no passing start is negative)
+  int32_t prev_c = 0;
+  for (int64_t base = a.w_lo; base < a.w_hi; base += kThreads) {
+    const int64_t w = base + tid;
+    bool el = false;
+    int64_t s = -1;
+    int32_t c = 0;
+    if (w < a.w_hi) {  // w - k >= 0, w + k < Wd, 0 <= w - lag < Wu
+      const int64_t u = w - a.lag;
+      const float p0 = dp[w], f0 = da[w], pm = dp[w - a.k], pp = dp[w + a.k];
+      const float p1 = up[u], f1 = ua[u];
+      const int iu = ui[u], id = di[w];
+      int sum = (iu + id) & (a.N - 1);
+      if (sum >= a.N / 2) sum -= a.N;
+      const int d = sum >> 1;  // floor
+      c = (iu - d) & (a.N - 1);
+      if (c >= a.N / 2) c -= a.N;
+      s = w * a.hop - (int64_t)d * a.osr - a.two_step;
+      el = p0 - f0 >= a.thresh_dn && p1 - f1 >= a.thresh_up && p0 >= pm && p0 > pp &&
+           (c < 0 ? -c : c) <= a.max_cfo && s >= 0 && s <= a.last_start;
+    }
+    const unsigned long long m = __ballot(el);
+    st[tid] = s;
+    cf_[tid] = c;
+    if (lane == 0) elig[wave] = m;
+    __syncthreads();
+    bool list = false;
+    if (el) {
+      int64_t ps = prev_s;
+      int32_t pc = prev_c;
+      int at = -1;
+      if (m & below) {
+        at = wave * 64 + 63 - __clzll((long long)(m & below));
+      } else {
+        int v = wave - 1;
+        while (v >= 0 && elig[v] == 0ull) --v;
+        if (v >= 0) at = v * 64 + 63 - __clzll((long long)elig[v]);
+      }
+      if (at >= 0) {
+        ps = st[at];
+        pc = cf_[at];
+      }
+      list = ps != s || pc != c;
+    }
+    const unsigned long long ml = __ballot(list);
+    if (lane == 0) listed[wave] = ml;
+    __syncthreads();
+    int before = 0, total = 0, lastw = -1;
+    for (int v = 0; v < kWaves; ++v) {
+      const int n = __popcll(listed[v]);
+      if (v < wave) before += n;
+      total += n;
+      if (elig[v] != 0ull) lastw = v;
+    }
+    if (list) {
+      const int64_t pos = cnt + before + __popcll(ml & below);
+      if (pos < a.capacity) {
+        starts[pos] = s;
+        cfo[pos] = c;
+      }
+    }
+    if (lastw >= 0) {
+      const int at = lastw * 64 + 63 - __clzll((long long)elig[lastw]);
+      prev_s = st[at];
+      prev_c = cf_[at];
+    }
+    cnt += total;
+    __syncthreads();  // st, cf_, elig and listed are rewritten by the next turn
+  }
+  if (tid == 0) a.count[row] = (int32_t)cnt;  // cnt <= Wd < 2^31
+  for (int64_t i = (cnt < a.capacity ? cnt : a.capacity) + tid; i < a.capacity; i += kThreads) {
+    starts[i] = -1;
+    cfo[i] = 0;
   }
 }
 
@@ -485,10 +618,98 @@ int64_t lora_find_candidates_batch(const lora_find_params* p, const float* power
   return e != hipSuccess ? lora::hip_error("k_find_candidates", e) : rows;
 }
 
+int64_t lora_find_preamble_batch(const lora_preamble_params* p, const float* up_power, const float* up_avg,
+                                 const uint16_t* up_index, int64_t Wu, int64_t up_stride, const float* dn_power,
+                                 const float* dn_avg, const uint16_t* dn_index, int64_t Wd, int64_t dn_stride,
+                                 int64_t rows, int64_t row_len, int64_t capacity, int64_t* starts,
+                                 int32_t* cfo_bins, int32_t* count, void* stream) {
+  if (!p) return set_last_error(LORA_EINVAL, "null params");
+  if (p->sf < 7 || p->sf > 12) return set_last_error(LORA_EINVAL, "the preamble finder needs SF 7-12");
+  if (p->osr < 1 || p->osr > (1u << 16)) return set_last_error(LORA_EINVAL, "osr must be in 1..65536");
+  const int64_t N = int64_t(1) << p->sf, step = N * (int64_t)p->osr;
+  if (p->hop < 1 || step % p->hop != 0 || step / p->hop < 4)
+    return set_last_error(LORA_EINVAL, "hop must divide step = N * osr at least four times");
+  if (p->acc_up < 2 || p->acc_up > 8) return set_last_error(LORA_EINVAL, "acc_up must be in 2..8");
+  if (p->max_cfo_bins < 0 || p->max_cfo_bins > N / 4 - 1)
+    return set_last_error(LORA_EINVAL, "max_cfo_bins must be in 0 .. N/4 - 1");
+  if (rows < 0 || Wu < 0 || Wd < 0 || up_stride < 0 || dn_stride < 0 || row_len < 0 || capacity < 0)
+    return set_last_error(LORA_EINVAL, "negative rows / W / stride / row_len / capacity");
+  if (Wu >= (int64_t(1) << 31) || Wd >= (int64_t(1) << 31)) return set_last_error(LORA_EINVAL, "W must be < 2^31");
+  if (rows >= (int64_t(1) << 31)) return set_last_error(LORA_EINVAL, "batch too large");
+  if (rows > 1 && (up_stride < Wu || dn_stride < Wd))
+    return set_last_error(LORA_EINVAL, "stride smaller than windows per row");
+  if (rows == 0) return 0;
+  if (!count || (capacity > 0 && (!starts || !cfo_bins))) return set_last_error(LORA_EINVAL, "null output");
+  const int64_t k = step / p->hop, lag = (2 + (int64_t)p->acc_up) * k;
+  const int64_t w_hi = Wd - k < Wu + lag ? Wd - k : Wu + lag;
+  if (w_hi > lag && (!up_power || !up_avg || !up_index || !dn_power || !dn_avg || !dn_index))
+    return set_last_error(LORA_EINVAL, "null metrics");
+  lora::PreambleArgs a{};
+  a.up_power = up_power;
+  a.up_avg = up_avg;
+  a.up_index = up_index;
+  a.dn_power = dn_power;
+  a.dn_avg = dn_avg;
+  a.dn_index = dn_index;
+  a.up_stride = up_stride;
+  a.dn_stride = dn_stride;
+  a.w_lo = lag;
+  a.w_hi = w_hi;
+  a.lag = lag;
+  a.hop = p->hop;
+  a.osr = p->osr;
+  a.two_step = 2 * step;
+  a.capacity = capacity;
+  a.last_start = row_len - 10 * step - 9 * step / 4;
+  a.starts = starts;
+  a.cfo = cfo_bins;
+  a.count = count;
+  a.k = (int)k;
+  a.N = (int)N;
+  a.max_cfo = p->max_cfo_bins;
+  a.thresh_up = p->thresh_up_db;
+  a.thresh_dn = p->thresh_dn_db;
+  lora::DeviceGuard guard(p->device);
+  if (guard.err != hipSuccess) return lora::hip_error("find device", guard.err);
+  hipLaunchKernelGGL(lora::k_find_preamble, dim3((unsigned)rows), dim3(lora::kThreads), 0,
+                     static_cast<hipStream_t>(stream), a);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? lora::hip_error("k_find_preamble", e) : rows;
+}
+
+// lora_select_frames_batch (tail == 0, no words) and lora_select_preamble_batch: one validation,
+// one kernel
+static int64_t select_entry(const int64_t* cand_starts, const int32_t* cand_word, const int32_t* status,
+                            const int32_t* nsym, int64_t rows, int64_t slots, const int64_t* first, int64_t row_len,
+                            int64_t step, int64_t tail, int64_t max_symbols, int64_t capacity, int64_t* starts,
+                            int32_t* out_word, int32_t* out_nsym, int32_t* count, int64_t* end, int device,
+                            void* stream);
+
+int64_t lora_select_preamble_batch(const int64_t* cand_starts, const int32_t* cand_word, const int32_t* status,
+                                   const int32_t* nsym, int64_t rows, int64_t slots, const int64_t* first,
+                                   int64_t row_len, int64_t step, int64_t tail, int64_t max_symbols,
+                                   int64_t capacity, int64_t* starts, int32_t* out_word, int32_t* out_nsym,
+                                   int32_t* count, int64_t* end, int device, void* stream) {
+  if (tail < 0) return set_last_error(LORA_EINVAL, "tail must be >= 0");
+  if (rows > 0 && slots > 0 && capacity > 0 && (cand_word == nullptr) != (out_word == nullptr))
+    return set_last_error(LORA_EINVAL, "cand_word and out_word go together");
+  return select_entry(cand_starts, cand_word, status, nsym, rows, slots, first, row_len, step, tail, max_symbols,
+                      capacity, starts, out_word, out_nsym, count, end, device, stream);
+}
+
 int64_t lora_select_frames_batch(const int64_t* cand_starts, const int32_t* status, const int32_t* nsym,
                                  int64_t rows, int64_t slots, const int64_t* first, int64_t row_len, int64_t step,
                                  int64_t max_symbols, int64_t capacity, int64_t* starts, int32_t* out_nsym,
                                  int32_t* count, int64_t* end, int device, void* stream) {
+  return select_entry(cand_starts, nullptr, status, nsym, rows, slots, first, row_len, step, 0, max_symbols, capacity,
+                      starts, nullptr, out_nsym, count, end, device, stream);
+}
+
+static int64_t select_entry(const int64_t* cand_starts, const int32_t* cand_word, const int32_t* status,
+                            const int32_t* nsym, int64_t rows, int64_t slots, const int64_t* first, int64_t row_len,
+                            int64_t step, int64_t tail, int64_t max_symbols, int64_t capacity, int64_t* starts,
+                            int32_t* out_word, int32_t* out_nsym, int32_t* count, int64_t* end, int device,
+                            void* stream) {
   if (rows < 0 || slots < 0 || row_len < 0 || capacity < 0 || step < 1 || max_symbols < 0)
     return set_last_error(LORA_EINVAL, "negative rows / slots / row_len / capacity / max_symbols, or step < 1");
   if (rows >= (int64_t(1) << 31) || slots >= (int64_t(1) << 31) || max_symbols >= (int64_t(1) << 31))
@@ -497,6 +718,9 @@ int64_t lora_select_frames_batch(const int64_t* cand_starts, const int32_t* stat
   if (!count || !end || (capacity > 0 && (!starts || !out_nsym))) return set_last_error(LORA_EINVAL, "null output");
   if (slots > 0 && (!cand_starts || !status || !nsym)) return set_last_error(LORA_EINVAL, "null slots");
   lora::SelectArgs a{};
+  a.tail = tail;
+  a.word = slots > 0 ? cand_word : nullptr;
+  a.out_word = capacity > 0 ? out_word : nullptr;
   a.starts = cand_starts;
   a.status = status;
   a.nsym = nsym;

@@ -194,6 +194,13 @@ __host__ __device__ constexpr int metrics_group(int sf) { return sf >= 6 ? 4096 
 int64_t scan_windows(int64_t row_len, int64_t step, int64_t hop);
 int64_t scan_grid(int sf, int64_t W, int64_t rows);
 int launch_detect_scan(const KArgs& a, const lora_symbol_metrics& o, int64_t rows, int64_t hop, hipStream_t st);
+// The accumulating scan (lora_scan.hip, k_detect_scan_acc).  scan_acc_windows: Wa = W - (acc - 1) *
+// (step / hop), or 0 (acc > 1: hop divides step, the caller has checked).  launch_detect_scan_acc:
+// as launch_detect_scan with the spectra of acc windows a symbol apart summed, the samples
+// conjugated first when conj is set; the caller has checked scan_grid(sf, Wa, rows) > 0.
+int64_t scan_acc_windows(int64_t row_len, int64_t step, int64_t hop, int64_t acc);
+int launch_detect_scan_acc(const KArgs& a, int64_t rows, int64_t hop, int acc, int conj, float* power,
+                           float* power_avg, uint16_t* index, int64_t out_stride, hipStream_t st);
 
 // ---- launch recording: the C++ drop-in's allocation-free dispatch (lora_aql.hip) -------
 // Every kernel launch of lora_demod_batch goes through lora::launch.  Normally that is

@@ -48,6 +48,11 @@ EXPORTED_SYMBOLS = (
     "lora_find_frames_batch",
     "lora_find_candidates_batch",
     "lora_select_frames_batch",
+    "lora_preamble_tables",
+    "lora_detect_scan_acc_windows",
+    "lora_detect_scan_acc_batch",
+    "lora_find_preamble_batch",
+    "lora_select_preamble_batch",
     "lora_channelize_outputs",
     "lora_channelize_batch",
     "lora_resample_outputs",
@@ -150,6 +155,21 @@ class FindParams(C.Structure):
     ]
 
 
+class PreambleParams(C.Structure):
+    """lora_preamble_params: the preamble finder's geometry, thresholds and device."""
+
+    _fields_ = [
+        ("sf", C.c_uint),
+        ("osr", C.c_uint),
+        ("hop", C.c_int64),
+        ("acc_up", C.c_int),
+        ("thresh_up_db", C.c_float),
+        ("thresh_dn_db", C.c_float),
+        ("max_cfo_bins", C.c_int),
+        ("device", C.c_int),
+    ]
+
+
 # windows per tile of the finder kernel's pass (lora_find_frames_tile; tests/test_find_capi.py
 # holds the two together)
 FIND_TILE = 4096
@@ -219,6 +239,26 @@ def lib() -> C.CDLL:
     L.lora_select_frames_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                            C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    # preambled frames: the tables (host arithmetic), the accumulating scan (csrc/lora_scan.hip),
+    # the preamble finder and the selection with a tail and a carried word (csrc/lora_find.hip)
+    L.lora_preamble_tables.restype = C.c_int64
+    L.lora_preamble_tables.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_float, C.c_int64, C.c_void_p, C.c_void_p]
+    L.lora_detect_scan_acc_windows.restype = C.c_int64
+    L.lora_detect_scan_acc_windows.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64]
+    L.lora_detect_scan_acc_batch.restype = C.c_int64
+    L.lora_detect_scan_acc_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                             C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                             C.c_void_p]
+    L.lora_find_preamble_batch.restype = C.c_int64
+    L.lora_find_preamble_batch.argtypes = [C.POINTER(PreambleParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                           C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]
+    L.lora_select_preamble_batch.restype = C.c_int64
+    L.lora_select_preamble_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                             C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p]
     # the down-converter bank (csrc/lora_channelize.hip)
     L.lora_channelize_outputs.restype = C.c_int64
     L.lora_channelize_outputs.argtypes = [C.c_int64, C.c_int64, C.c_int64]

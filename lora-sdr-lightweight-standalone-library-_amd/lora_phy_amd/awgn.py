@@ -293,7 +293,8 @@ def sweep_receive(sf: int, snr_dbs: Sequence[float], frames: int = 2000, frame_s
 def sweep_receive_frames(sf: int, snr_dbs: Sequence[float], frames: int = 1000, max_bytes: int = 16, cr=1,
                          osr: int = 1, hop: Optional[int] = None, thresh_db: float = 0.0, seed: int = 1234,
                          frames_per_row: int = 4, noise_windows: int = 0, noise_batch_samples: int = 1 << 26,
-                         sync: int = 0x12, device=None, soft: bool = False, max_flips: int = 5) -> List[Dict]:
+                         sync: int = 0x12, device=None, soft: bool = False, max_flips: int = 5,
+                         cfo_bins: float = 0.0) -> List[Dict]:
     """``sweep_receive`` for frames that state their own length: what ``stream.receive_frames_device``
     returns under ``stream.impair``, with no frame length given to it.
 
@@ -315,7 +316,9 @@ def sweep_receive_frames(sf: int, snr_dbs: Sequence[float], frames: int = 1000, 
     runs on the device; the counts of all points come to the host in one copy at the end.
 
     ``soft`` and ``max_flips`` go to ``receive_frames_device``: the rows and their noise do not
-    depend on them, so the same seeded rows can be received both ways.  The records carry them."""
+    depend on them, so the same seeded rows can be received both ways.  The records carry them.
+    ``cfo_bins``: a carrier offset of that many bins (``cfo_bins / step`` cycles per sample) put on
+    the rows by the same ``impair`` call; 0 (the default) performs no rotation at all."""
     from . import codec, stream
 
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -366,7 +369,8 @@ def sweep_receive_frames(sf: int, snr_dbs: Sequence[float], frames: int = 1000, 
                             got.candidates.sum(), (got.candidates.to(torch.int64) - C).clamp_min(0).sum()])
 
     for i, snr in enumerate(snr_dbs):
-        stream.impair(clean, snr_db=float(snr), seed=seed, first_row=i * R, out=work)
+        stream.impair(clean, snr_db=float(snr), seed=seed, first_row=i * R, out=work,
+                      cfo=(float(cfo_bins) / step) if cfo_bins else None)
         counts.append(tally(stream.receive_frames_device(plan, work, S, hop, sync, thresh_db, soft=soft,
                                                          max_flips=max_flips)))
     noise_counts, noise_total = [], 0
@@ -401,6 +405,128 @@ def sweep_receive_frames(sf: int, snr_dbs: Sequence[float], frames: int = 1000, 
                     "candidates_per_window": cands / noise_total,
                     "candidate_capacity_per_window": hop / (4 * step),
                     "false_frames_per_million_windows": false * 1e6 / noise_total})
+    if soft:
+        for rec in out:
+            rec.update(soft=True, max_flips=int(max_flips))
+    return out
+
+
+def sweep_receive_preamble(sf: int, snr_dbs: Sequence[float], frames: int = 1000, max_bytes: int = 16, cr=1,
+                           osr: int = 1, hop: Optional[int] = None, thresh_up_db: float = 0.0,
+                           thresh_dn_db: float = 0.0, preamble: int = 8, preamble_acc: int = 6,
+                           cfo_bins: float = 0.0, max_cfo_bins: Optional[int] = None, seed: int = 1234,
+                           frames_per_row: int = 4, noise_windows: int = 0, noise_batch_samples: int = 1 << 26,
+                           sync: int = 0x12, device=None, soft: bool = False, max_flips: int = 5,
+                           cand_capacity_mult: int = 1) -> List[Dict]:
+    """``sweep_receive_frames`` for preambled frames: what ``stream.receive_preamble_frames_device``
+    returns under ``stream.impair`` with a carrier offset of ``cfo_bins`` bins.  The payloads, their
+    lengths and the gaps are drawn from ``seed`` in ``sweep_receive_frames``' order, so the two
+    sweeps carry the same payloads; here every frame has ``preamble`` up-chirps in front and the
+    delimiter inside (``modulate_preamble``), and a planted start is the frame's first sync symbol.
+
+    The records are ``sweep_receive_frames``' plus ``cfo_right``: the planted frames returned with
+    the exact payload whose reported offset is ``round(cfo_bins)`` (``returned_ok`` does not ask for
+    it).  The noise-only record counts the candidates of the preamble finder.
+    ``cand_capacity_mult``: the candidate capacity as a multiple of the chain's default (one slot
+    per four symbols of the row), to tell frames lost to a full candidate list from frames not
+    found; ``candidates_dropped`` counts against the capacity used."""
+    from . import codec, stream
+    from .mod import modulate_preamble
+
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    N = 1 << sf
+    step = N * osr
+    tail = 9 * step // 4
+    hop = step // 4 if hop is None else int(hop)
+    K, B, P = int(frames_per_row), int(max_bytes), int(preamble)
+    R = -(-int(frames) // K)
+    F = R * K
+    S = codec.frame_symbols(sf, cr, B)
+    rng = np.random.default_rng(seed)
+    nbytes = rng.integers(0, B + 1, (R, K))
+    nsym = np.vectorize(lambda n: codec.frame_symbols(sf, cr, int(n)))(nbytes)
+    length = (P + 2 + nsym) * step + tail                                        # [R, K]
+    gaps = rng.integers(0, 2 * N, (R, K + 1)) * osr
+    begins = np.cumsum(gaps[:, :K], axis=1) + np.cumsum(length, axis=1) - length
+    starts = begins + P * step                                                   # the first sync symbol
+    L = int((begins[:, -1] + length[:, -1] + gaps[:, K]).max())
+    pay = rng.integers(0, 256, (F, B)).astype(np.uint8)
+    pay[np.arange(B)[None, :] >= nbytes.reshape(-1, 1)] = 0
+    plan = DemodPlan(sf, osr, 125000, "none", dechirp=True, mode="legacy", device=dev)
+    starts_t = torch.from_numpy(starts).to(dev)
+    pay_t = torch.from_numpy(pay).to(dev).view(R, K, B)
+    nbytes_t = torch.from_numpy(nbytes.astype(np.int32)).to(dev)
+    symbols, _ = codec.encode_frame(pay_t.view(F, B), nbytes_t.view(-1), sf, cr)
+    rows = modulate_preamble(symbols, sf, osr, 125000, 1.0, sync, P)             # [F, (P + 2 + S) * step + tail]
+    clean = torch.zeros((R, L), dtype=torch.complex64, device=dev)
+    at = (torch.arange(R, device=dev)[:, None] * L + torch.from_numpy(begins).to(dev)).reshape(-1)
+    live = torch.arange(rows.shape[1], device=dev)[None, :] < torch.from_numpy(length).to(dev).reshape(-1, 1)
+    clean.view(-1)[(at[:, None] + torch.arange(rows.shape[1], device=dev))[live]] = rows[live]
+    del rows, live
+    work = torch.empty_like(clean)
+    W = (L - step) // hop + 1
+    want_c = int(round(float(cfo_bins)))
+    counts = []
+
+    mult = int(cand_capacity_mult)
+
+    def receive(x):
+        return stream.receive_preamble_frames_device(plan, x, S, preamble_acc, hop, sync, thresh_up_db, thresh_dn_db,
+                                                     max_cfo_bins, cand_capacity=mult * -(-x.shape[1] // (4 * step)),
+                                                     soft=soft, max_flips=max_flips)
+
+    def tally(got):
+        valid = got.found.valid                                                  # [R, cap]
+        cap = valid.shape[1]
+        same = got.found.starts[:, :, None] == starts_t[:, None, :]              # [R, cap, K]
+        hit = same.any(2) & valid
+        which = same.to(torch.int8).argmax(2)
+        ok = got.frames.status.view(R, cap) == codec.FRAME_OK
+        want = torch.gather(pay_t, 1, which[:, :, None].expand(-1, -1, B))
+        want_n = torch.gather(nbytes_t, 1, which)
+        rx = got.frames.payload.view(R, cap, got.frames.payload.shape[-1])[:, :, :B]
+        right = hit & ok & (got.frames.nbytes.view(R, cap) == want_n) & (rx == want).all(2)
+        C = got.found.starts.new_tensor(mult * -(-L // (4 * step)))
+        return torch.stack([right.sum(), hit.sum(), (valid & ~hit).sum(), (valid & ~hit & ok).sum(),
+                            got.candidates.sum(), (got.candidates.to(torch.int64) - C).clamp_min(0).sum(),
+                            (right & (got.cfo_bins == want_c)).sum()])
+
+    for i, snr in enumerate(snr_dbs):
+        stream.impair(clean, snr_db=float(snr), seed=seed, first_row=i * R, out=work,
+                      cfo=(float(cfo_bins) / step) if cfo_bins else None)
+        counts.append(tally(receive(work)))
+    noise_counts, noise_total = [], 0
+    if noise_windows > 0:
+        Ln = max((P + S + 6) * step, min(int(noise_batch_samples), 1 << 22))
+        Rn = max(1, int(noise_batch_samples) // Ln)
+        Wn = (Ln - step) // hop + 1
+        Cn = mult * -(-Ln // (4 * step))
+        buf = torch.empty((Rn, Ln), dtype=torch.complex64, device=dev)
+        b = 0
+        while noise_total < noise_windows:
+            stream.impair(None, sigma=1.0, seed=seed + 1, first_row=b * Rn, out=buf, rows=Rn, length=Ln, device=dev)
+            got = receive(buf)
+            ok = (got.frames.status.view(Rn, -1) == codec.FRAME_OK) & got.found.valid
+            noise_counts.append(torch.stack([got.found.count.sum(), ok.sum(), got.candidates.sum(),
+                                             (got.candidates.to(torch.int64) - Cn).clamp_min(0).sum()]))
+            noise_total += Rn * Wn
+            b += 1
+    got = torch.stack(counts).cpu().numpy() if counts else np.zeros((0, 7), np.int64)  # the synchronisation
+    out = []
+    common = {"sf": sf, "osr": osr, "hop": hop, "thresh_up_db": float(thresh_up_db),
+              "thresh_dn_db": float(thresh_dn_db), "preamble": P, "preamble_acc": int(preamble_acc),
+              "cfo_bins": float(cfo_bins), "max_symbols": S, "cand_capacity_mult": mult}
+    for snr, (right, hit, false, false_ok, cands, dropped, cfo_right) in zip(snr_dbs, got.tolist()):
+        out.append(dict(common, snr_db=float(snr), max_bytes=B, rdd=codes.rdd_of(cr), planted=F, returned_ok=right,
+                        cfo_right=cfo_right, found_at_planted=hit, false_frames=false, false_frames_ok=false_ok,
+                        candidates=cands, candidates_dropped=dropped, windows=R * W, p_ok=right / F,
+                        false_frames_per_million_windows=false * 1e6 / (R * W)))
+    if noise_counts:
+        false, false_ok, cands, dropped = torch.stack(noise_counts).sum(0).cpu().tolist()
+        out.append(dict(common, noise_only=True, windows=noise_total, false_frames=false, false_frames_ok=false_ok,
+                        candidates=cands, candidates_dropped=dropped, candidates_per_window=cands / noise_total,
+                        candidate_capacity_per_window=hop / (4 * step),
+                        false_frames_per_million_windows=false * 1e6 / noise_total))
     if soft:
         for rec in out:
             rec.update(soft=True, max_flips=int(max_flips))

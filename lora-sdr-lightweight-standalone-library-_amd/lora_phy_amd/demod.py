@@ -406,6 +406,44 @@ class DemodPlan:
         assert got == W, (got, W)
         return out
 
+    def scan_acc(self, iq: torch.Tensor, hop: int, acc: int, conj: bool = False,
+                 out: Optional[DetectMetrics] = None) -> DetectMetrics:
+        """The accumulating scan (lora_detect_scan_acc_batch): ``scan`` with the |X|^2 spectra of
+        ``acc`` (1..8) windows one symbol apart summed in fp32, oldest first, before the detector's
+        argmax and noise floor - column w of the [R, Wa] result covers the ``acc`` symbols from
+        ``w * hop``, ``Wa = max(scan_windows(L, hop) - (acc - 1) * (step // hop), 0)``.  With
+        ``acc > 1`` ``hop`` must divide ``step``.  ``conj``: the scan of the conjugated rows, in
+        which a down-chirp dechirps as an up-chirp does.  Returns DetectMetrics with ``f_index``
+        None (a summed spectrum has no neighbour phases).  ``acc=1`` equals ``scan`` bit for bit.
+        ``out`` follows ``scan``'s rules with Wa for W; its ``f_index`` must be None.  One kernel on
+        the current stream, nothing allocated besides the outputs; nothing synchronises."""
+        iq = _check_iq(iq, self.device)
+        R, L = iq.shape
+        hop, acc = int(hop), int(acc)
+        if hop < 1:
+            raise ValueError("hop must be >= 1")
+        if not 1 <= acc <= 8:
+            raise ValueError("acc must be in 1..8")
+        if acc > 1 and self.step % hop:
+            raise ValueError(f"with acc > 1, hop must divide step = {self.step} (got {hop})")
+        W = 0 if L < self.step else (L - self.step) // hop + 1
+        Wa = max(W - (acc - 1) * (self.step // hop), 0) if acc > 1 else W
+        dev = self.device
+        if out is None:
+            out = DetectMetrics(torch.empty((R, Wa), dtype=torch.float32, device=dev),
+                                torch.empty((R, Wa), dtype=torch.float32, device=dev), None,
+                                torch.empty((R, Wa), dtype=torch.uint16, device=dev))
+        elif out.f_index is not None:
+            raise ValueError("scan_acc has no f_index: out.f_index must be None")
+        out, m = _metric_outputs(out, R, Wa, dev)
+        stride = iq.stride(0) if R > 1 else L
+        if R and Wa:
+            got = _capi.check(self._lib.lora_detect_scan_acc_batch(
+                self._h, iq.data_ptr(), R, L, stride, hop, acc, 1 if conj else 0, m.power, m.power_avg, m.index,
+                m.stride, _stream_handle(dev)))
+            assert got == Wa, (got, Wa)
+        return out
+
     def estimate_offsets(self, iq: torch.Tensor, cfo: torch.Tensor, time_offset: torch.Tensor) -> int:
         """phy.cpp:78-145 over every whole symbol of each frame (raw samples)."""
         iq = _check_iq(iq, self.device)
@@ -626,6 +664,23 @@ class LoRaDemod:
         got = stream.receive_wideband_frames_device(self.plan, chan, iq, self.mtu if max_symbols is None
                                                     else max_symbols, hop, self.sync, thresh_db, scale, first,
                                                     capacity, cand_capacity)
+        self.last = got.result
+        return got
+
+    def work_preamble_device(self, iq: torch.Tensor, max_symbols: Optional[int] = None, preamble_acc: int = 6,
+                             hop: Optional[int] = None, thresh_up_db: Optional[float] = None,
+                             thresh_dn_db: Optional[float] = None, max_cfo_bins: Optional[int] = None, first=None, capacity: Optional[int] = None,
+                             cand_capacity: Optional[int] = None, soft: bool = False, max_flips: int = 5):
+        """``work_packets_device`` for preambled frames (``LoRaMod.work_frame(preamble=...)``) under a
+        carrier offset of whole bins (``lora_phy_amd.stream.receive_preamble_frames_device`` with this
+        block's plan): the StreamPackets also hold each frame's ``cfo_bins``.  Nothing
+        synchronises."""
+        from . import stream
+
+        got = stream.receive_preamble_frames_device(self.plan, iq, self.mtu if max_symbols is None else max_symbols,
+                                                    preamble_acc, hop, self.sync, thresh_up_db, thresh_dn_db,
+                                                    max_cfo_bins, first, capacity, cand_capacity, soft=soft,
+                                                    max_flips=max_flips)
         self.last = got.result
         return got
 

@@ -41,6 +41,53 @@ def modulate(symbols: torch.Tensor, sf: int, osr: int = 1, bw: int = 125000,
     return out[0] if squeeze else out
 
 
+_PREAMBLE_TABLES = {}
+
+
+def preamble_tables(sf: int, osr: int = 1, bw: int = 125000, amplitude: float = 1.0, preamble: int = 8,
+                    device=None):
+    """The two fixed parts of a preambled frame (include/lora_mi355x.h, "Preambled frames") as
+    complex64 device tensors: ``(pre, sfd)`` - ``preamble`` up-chirps (``preamble * step``
+    samples) and the start-of-frame delimiter, two down-chirps and a quarter (``9 * step // 4``).
+    Computed once per configuration on the host (lora_preamble_tables) and kept on the device."""
+    osr = int(osr) if osr else 1
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise TypeError("preamble_tables lives on a CUDA (HIP) device; there is no CPU fallback")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    key = (int(sf), osr, int(bw), float(amplitude), int(preamble), dev.index)
+    if key not in _PREAMBLE_TABLES:
+        lib = _capi.lib()
+        n = _capi.check(lib.lora_preamble_tables(int(sf), osr, int(bw), float(amplitude), int(preamble), None, None))
+        step = n // int(preamble)
+        pre = torch.empty(n, dtype=torch.complex64)
+        sfd = torch.empty(9 * step // 4, dtype=torch.complex64)
+        _capi.check(lib.lora_preamble_tables(int(sf), osr, int(bw), float(amplitude), int(preamble), pre.data_ptr(),
+                                             sfd.data_ptr()))
+        _PREAMBLE_TABLES[key] = (pre.to(dev), sfd.to(dev))
+    return _PREAMBLE_TABLES[key]
+
+
+def _with_preamble(iq: torch.Tensor, step: int, pre: torch.Tensor, sfd: torch.Tensor) -> torch.Tensor:
+    """[pre | iq[.., :2 * step] | sfd | iq[.., 2 * step:]] along the last dimension."""
+    lead = iq.shape[:-1]
+    return torch.cat([pre.expand(lead + pre.shape), iq[..., :2 * step], sfd.expand(lead + sfd.shape),
+                      iq[..., 2 * step:]], dim=-1)
+
+
+def modulate_preamble(symbols: torch.Tensor, sf: int, osr: int = 1, bw: int = 125000, amplitude: float = 1.0,
+                      sync: int = 0x12, preamble: int = 8) -> torch.Tensor:
+    """``modulate`` with a preamble and a start-of-frame delimiter: per frame ``preamble`` up-chirps,
+    the two sync symbols, two and a quarter down-chirps, the data symbols - ``(preamble + 2 + S) *
+    step + 9 * step // 4`` samples.  The sync and data parts are ``modulate``'s frame bit for bit;
+    the phase is not continuous across the three joins (include/lora_mi355x.h says why).
+    ``modulate`` and one ``torch.cat``: transmit is not the hot path."""
+    iq = modulate(symbols, sf, osr, bw, amplitude, sync)
+    pre, sfd = preamble_tables(sf, osr, bw, amplitude, preamble, iq.device)
+    return _with_preamble(iq, (1 << int(sf)) * (int(osr) if osr else 1), pre, sfd)
+
+
 class LoRaMod:
     """Block-style modulator mirroring the Pothos ``/lora/lora_mod`` surface
     (examples/lora_simulation.pth:312-326: sf, sync, padding, ampl, ovs) plus bw."""
@@ -79,13 +126,16 @@ class LoRaMod:
             frames = frames.unsqueeze(0)
         return stream.transmit_wideband(synth, frames, channel, starts, chan_len, dtype=dtype)
 
-    def work_frame(self, payload, nbytes=None, crc: bool = True) -> torch.Tensor:
+    def work_frame(self, payload, nbytes=None, crc: bool = True, preamble: Optional[int] = None) -> torch.Tensor:
         """Self-describing frames (``codec.encode_frame`` at this block's ``sf`` and ``cr``), then
         modulated: ``payload`` is uint8 [F, max_bytes] (or [max_bytes]), of which frame f carries
         ``nbytes[f]`` bytes (an int32 [F] tensor or a sequence; None: max_bytes each).  Every row
         is as long as the longest possible frame; a shorter frame is followed by silence - zero
         samples, not zero symbols - so a receiver sees nothing after its last symbol.  Nothing is
-        read back: the frame lengths stay on the device.  (SF 7-12.)"""
+        read back: the frame lengths stay on the device.  (SF 7-12.)  ``preamble`` (4..64): each
+        frame as a preambled frame (``modulate_preamble``: that many up-chirps in front, the
+        delimiter between the sync symbols and the data), the silence after it as before; ``work``'s
+        padding then follows the frame."""
         from . import codec
 
         if not isinstance(payload, torch.Tensor):
@@ -98,7 +148,10 @@ class LoRaMod:
         step = (1 << self.sf) * self.ovs
         live = torch.arange(iq.shape[-1], device=self.device) < ((nsym.to(torch.int64) + 2) * step)[:, None]
         zero = torch.zeros((), dtype=iq.dtype, device=self.device)
-        return torch.where(live if iq.dim() == 2 else live[0], iq, zero)
+        iq = torch.where(live if iq.dim() == 2 else live[0], iq, zero)
+        if preamble is None:
+            return iq
+        return _with_preamble(iq, step, *preamble_tables(self.sf, self.ovs, self.bw, self.ampl, preamble, self.device))
 
     def work_payload(self, payload, chain: str = "library", append_crc: bool = False) -> torch.Tensor:
         """Encode payload bytes ([F, n] or [n] uint8) on the device (lora_phy_amd.codec), then

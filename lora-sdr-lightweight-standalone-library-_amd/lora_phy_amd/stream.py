@@ -78,8 +78,52 @@ Of 20,000 random 8-symbol headers per SF, 2 to 5 pass the header's checks, so th
 the guard against false candidates that a negative ``thresh_db`` admits - the experiment the
 measurement above left open; DESIGN.md §6n has what was measured.  Limits: bw 125 kHz and the
 ``hop`` rules as above, SF 7-12 (the header block carries ``sf - 7`` data nibbles), hard decisions
-only, no implicit-header mode, no preamble or SFD, and no claim of decoding a real LoRa radio.
+only, no implicit-header mode, and no claim of decoding a real LoRa radio.  (``soft=True`` decides
+on soft bits; frames with a preamble and a delimiter are the next paragraph's.)
 The host model of the chain lives in tests/frame_checker.py.
+
+Preambled frames under a carrier offset.  The finder above decides on two single windows and
+cannot tell an offset of whole bins from a timing shift: every start it returns moves by that many
+chips.  ``LoRaMod.work_frame(preamble=P)`` / ``modulate_preamble`` put ``P`` plain up-chirps in front
+of the two sync symbols and two and a quarter down-chirps (``tail = 9 * step // 4`` samples) between
+them and the data - the layout is this project's own, stated to the bit in include/lora_mi355x.h;
+each part starts at phase 0, so ``[sync | data]`` gathered from a preambled frame is the plain
+frame bit for bit - and ``receive_preamble_frames_device`` finds them from summed spectra:
+
+* ``up = plan.scan_acc(rows, hop, m)`` and ``dn = plan.scan_acc(rows, hop, 2, conj=True)``: the scan
+  with the |X|^2 spectra of ``m`` (``preamble_acc``, 2..8) and of 2 windows one symbol apart summed
+  in fp32 before the detector's argmax and floor; in the conjugated stream a down-chirp dechirps as
+  an up-chirp does.  ``k = step // hop >= 4``, SF 7-12, bw 125 kHz.
+* A window ``d`` chips late under an offset of ``c`` bins sees bin ``d + c`` on the up side and ``d -
+  c`` on the down side.  For down window ``w`` with ``(2 + m) * k <= w``, ``w + k < Wd`` and ``u = w -
+  (2 + m) * k < Wu``, all of: (1) ``dn.power[w] - dn.power_avg[w] >= thresh_dn_db`` and
+  ``up.power[u] - up.power_avg[u] >= thresh_up_db`` in fp32 (NaN fails, +inf passes); (2)
+  ``dn.power[w] >= dn.power[w - k]`` and ``dn.power[w] > dn.power[w + k]``: the symbol where both
+  summed windows lie on down-chirps; (3) ``s = (up.index[u] + dn.index[w]) mod N`` centred to
+  ``[-N/2, N/2)``, ``d = floor(s / 2)``, ``c = (up.index[u] - d) mod N`` centred, and ``|c| <=
+  max_cfo_bins`` (0 .. N/4 - 1), which rejects the ``(d +- N/2, c +- N/2)`` alias that windows near a
+  quarter symbol off produce; (4) ``start = w * hop - d * osr - 2 * step``, the first sync symbol,
+  with ``start >= 0`` and ``start + 10 * step + tail <= row_len``.
+* A candidate is listed in increasing ``w`` unless its ``(start, c)`` equals that of the previous
+  window that passed 1-4 (``find_preamble_device``).  Each is probed as above - gathered as
+  ``[sync | data]``, the delimiter skipped, and derotated by ``impair`` with the word ``floor(-c *
+  2**32 / step)`` (phase 0 at the slot's first sample, so the phase steps at the join, which a
+  demodulator that is non-coherent across symbols does not see) - and ``select_preamble_device``
+  runs the greedy pass with ``tail`` added to every frame's length, carrying ``c`` to the accepted
+  slot (``StreamPackets.cfo_bins``).
+
+Limits: integer bins only - the residual fraction stays with the demodulator's own estimate - no
+fractional delay or drift, ``preamble_acc <= P``, offsets up to ``N / 4 - 1`` bins, and the finder
+kernels take one workgroup per row (as ``find_candidates_device``).  The accumulating kernel
+recomputes the ``acc`` spectra of every output window (``acc`` times the plain scan's work); a form
+that transforms each window once is not built.  Measured once (profiles/stream/preamble_prob.json,
+``tools/preamble_prob.py``, DESIGN.md 6p: 600 frames per point, offsets 0 and 3.25 bins): under the
+offset the chain above returns no planted frame at any SNR and this one reports 3 bins on every
+frame it returns; the edge moves by at least 6 dB at SF12 (every frame at -20 dB), about 2 dB at
+SF9 and not at SF7, where header and payload fail with the finder; and at thresholds as low as
+noise alone allows (-16 / -22 / -28 dB) a frame's own data symbols list about 18 candidates and
+crowd the default candidate capacity, so the chain's thresholds default to 6 dB above those
+(``preamble_threshold_db``).  The host model lives in tests/preamble_checker.py.
 
 Wideband captures.  An SDR delivers one wideband stream that holds several LoRa channels at
 known offsets from the tuner frequency.  ``Channelizer`` is the stage in front of the scan: one
@@ -133,7 +177,9 @@ __all__ = ["find_frames", "extract_frames", "receive", "lowpass_taps", "nco_tabl
            "receive_wideband", "raw_scale", "raw_to_complex", "Synthesizer", "transmit_wideband",
            "FoundFrames", "StreamFrames", "find_frames_device", "receive_device", "receive_wideband_device",
            "impair", "cfo_word", "noise_sigma", "gather_frames_device", "StreamPackets", "find_candidates_device",
-           "select_frames_device", "receive_frames_device", "receive_wideband_frames_device"]
+           "select_frames_device", "receive_frames_device", "receive_wideband_frames_device",
+           "preamble_threshold_db", "find_preamble_device", "select_preamble_device", "receive_preamble_frames_device",
+           "receive_wideband_preamble_frames_device"]
 
 _NONE = -(1 << 62)  # "no candidate here" in the packed starts
 
@@ -775,6 +821,7 @@ class StreamPackets:
     frames: "object"          # codec.FrameResult of every slot: status, nbytes, rdd, has_crc, errors, payload
     candidates: torch.Tensor  # [R] int32: candidates listed per row (above cand_capacity: some were dropped)
     llr: Optional[torch.Tensor] = None  # soft=True: [R * capacity, 2 + max_symbols, sf] soft bits of the slots
+    cfo_bins: Optional[torch.Tensor] = None  # receive_preamble_frames_device: [R, capacity] int32 offsets in bins
 
 
 def _scan_rows(metrics: DetectMetrics, what: str):
@@ -1007,6 +1054,251 @@ def receive_wideband_frames_device(plan: DemodPlan, chan: "Channelizer", iq: tor
     rows = chan.run(iq, scale=scale)  # [C, Wc]
     return _receive_frame_rows(plan, rows, max_symbols, hop, sync, thresh_db, first, capacity, cand_capacity, soft,
                                max_flips)
+
+
+def _preamble_geometry(hop, sf, osr, acc_up, max_cfo_bins, bw):
+    sf, osr, hop, acc_up = int(sf), int(osr) if osr else 1, int(hop), int(acc_up)
+    if int(bw) != 125000:
+        raise ValueError("the preamble finder is defined at bw 125000 only")
+    if not 7 <= sf <= 12:
+        raise ValueError("the preamble finder needs SF 7-12")
+    N = 1 << sf
+    step = N * osr
+    if hop < 1 or step % hop != 0 or step // hop < 4:
+        raise ValueError(f"hop must divide step = {step} at least four times (got {hop})")
+    if not 2 <= acc_up <= 8:
+        raise ValueError("preamble_acc must be in 2..8")
+    max_cfo_bins = N // 4 - 1 if max_cfo_bins is None else int(max_cfo_bins)
+    if not 0 <= max_cfo_bins <= N // 4 - 1:
+        raise ValueError(f"max_cfo_bins must be in 0..{N // 4 - 1}")
+    return N, step, step // hop, 9 * step // 4, max_cfo_bins
+
+
+def preamble_threshold_db(sf: int) -> float:
+    """The default of both thresholds of the preambled chain, from the measurement in DESIGN.md
+    6p (profiles/stream/preamble_prob.json): -10 dB at SF7 and 3 dB lower per SF down to -22 dB -
+    6 dB above the lowest value noise alone allows, which is where a frame's own data symbols stop
+    crowding the candidate list.  SF 7, 9 and 12 were measured (-10, -16, -22); SF 8, 10 and 11 are
+    interpolated."""
+    return float(max(-10 - 3 * (int(sf) - 7), -22))
+
+
+def find_preamble_device(up: DetectMetrics, dn: DetectMetrics, hop: int, sf: int, osr: int, acc_up: int,
+                         thresh_up_db: float = 0.0, thresh_dn_db: float = 0.0, max_cfo_bins: Optional[int] = None,
+                         row_len: Optional[int] = None, cand_capacity: Optional[int] = None, bw: int = 125000):
+    """The preamble finder (lora_find_preamble_batch, one kernel; the rule is in this module's
+    docstring): ``up`` is ``plan.scan_acc(rows, hop, acc_up)``, ``dn`` is ``plan.scan_acc(rows, hop,
+    2, conj=True)`` of the same rows.  Returns ``(count, starts, cfo_bins)``: int32 [R] - the
+    candidates listed, which may exceed the capacity - int64 [R, cand_capacity] starts (the first
+    sync symbol; -1 beyond the count) and int32 [R, cand_capacity] carrier offsets in bins (0
+    beyond the count).  ``row_len`` defaults to the span the down scan covers; ``cand_capacity`` to
+    ``ceil(row_len / (4 * step))``; ``max_cfo_bins`` to ``N / 4 - 1``.  Nothing synchronises."""
+    N, step, k, tail, max_cfo_bins = _preamble_geometry(hop, sf, osr, acc_up, max_cfo_bins, bw)
+    hop, osr = int(hop), step // N
+    upw, upa, upi, ups = _scan_rows(up, "find_preamble_device")
+    dnw, dna, dni, dns = _scan_rows(dn, "find_preamble_device")
+    R, Wu = upw.shape
+    Wd = dnw.shape[1]
+    if dnw.shape[0] != R or dnw.device != upw.device:
+        raise ValueError("up and dn must be scans of the same rows on one device")
+    if row_len is None:
+        row_len = (Wd - 1) * hop + 2 * step if Wd else 0
+    row_len = int(row_len)
+    cap = _ceil_div(row_len, 4 * step) if cand_capacity is None else int(cand_capacity)
+    if row_len < 0 or cap < 0:
+        raise ValueError("row_len and cand_capacity must be >= 0")
+    dev = upw.device
+    count = torch.empty(R, dtype=torch.int32, device=dev)
+    starts = torch.empty((R, cap), dtype=torch.int64, device=dev)
+    cfo = torch.empty((R, cap), dtype=torch.int32, device=dev)
+    if R:
+        prm = _capi.PreambleParams(int(sf), osr, hop, int(acc_up), float(thresh_up_db), float(thresh_dn_db),
+                                   max_cfo_bins, dev.index)
+        ptr = lambda t, W: t.data_ptr() if W else None  # noqa: E731
+        _capi.check(_capi.lib().lora_find_preamble_batch(
+            _capi.C.byref(prm), ptr(upw, Wu), ptr(upa, Wu), ptr(upi, Wu), Wu, ups, ptr(dnw, Wd), ptr(dna, Wd),
+            ptr(dni, Wd), Wd, dns, R, row_len, cap, starts.data_ptr() if cap else None,
+            cfo.data_ptr() if cap else None, count.data_ptr(), _stream_handle(dev)))
+    return count, starts, cfo
+
+
+def select_preamble_device(cand_starts: torch.Tensor, cand_cfo: torch.Tensor, status: torch.Tensor,
+                           nsym: torch.Tensor, step: int, row_len: int, max_symbols: int,
+                           first: Union[None, int, torch.Tensor] = None, capacity: Optional[int] = None,
+                           tail: Optional[int] = None) -> Tuple[FoundFrames, torch.Tensor, torch.Tensor]:
+    """``select_frames_device`` for preambled frames (lora_select_preamble_batch, the same kernel):
+    a frame ends at ``start + (2 + nsym) * step + tail`` (``tail`` defaults to ``9 * step // 4``), and
+    each slot's ``cand_cfo`` (int32 [R, C]) is carried to the accepted slot - two candidates may share
+    a start with different offsets, so the offset cannot be looked up afterwards.  ``capacity``
+    defaults to ``row_len // (10 * step + tail)``.  Returns ``(found, nsym, cfo_bins)``; nothing
+    synchronises."""
+    for t, name, dt in ((cand_starts, "cand_starts", torch.int64), (cand_cfo, "cand_cfo", torch.int32),
+                        (status, "status", torch.int32), (nsym, "nsym", torch.int32)):
+        _require_cuda(t, name)
+        if t.dtype != dt:
+            raise TypeError(f"{name} must be {dt}, got {t.dtype}")
+        if t.dim() != 2 or t.shape != cand_starts.shape or t.device != cand_starts.device or not t.is_contiguous():
+            raise ValueError("cand_starts, cand_cfo, status and nsym must be contiguous [R, C] tensors on one device")
+    R, C = cand_starts.shape
+    dev = cand_starts.device
+    step, row_len, max_symbols = int(step), int(row_len), int(max_symbols)
+    tail = 9 * step // 4 if tail is None else int(tail)
+    first_t = _find_first(first, R, dev)
+    if first_t is not None and first_t.device != dev:
+        raise ValueError(f"first must be on {dev}")
+    capacity = row_len // (10 * step + tail) if capacity is None else int(capacity)
+    if capacity < 0 or tail < 0:
+        raise ValueError("capacity and tail must be >= 0")
+    found = FoundFrames(count=torch.empty(R, dtype=torch.int32, device=dev),
+                        starts=torch.empty((R, capacity), dtype=torch.int64, device=dev),
+                        end=torch.empty(R, dtype=torch.int64, device=dev))
+    out_nsym = torch.empty((R, capacity), dtype=torch.int32, device=dev)
+    out_cfo = torch.zeros((R, capacity), dtype=torch.int32, device=dev)
+    if R:
+        if first_t is not None and not first_t.is_contiguous():
+            first_t = first_t.contiguous()
+        both = C > 0 and capacity > 0
+        _capi.check(_capi.lib().lora_select_preamble_batch(
+            cand_starts.data_ptr() if C else None, cand_cfo.data_ptr() if both else None,
+            status.data_ptr() if C else None, nsym.data_ptr() if C else None, R, C,
+            first_t.data_ptr() if first_t is not None else None, row_len, step, tail, max_symbols, capacity,
+            found.starts.data_ptr() if capacity else None, out_cfo.data_ptr() if both else None,
+            out_nsym.data_ptr() if capacity else None, found.count.data_ptr(), found.end.data_ptr(), dev.index,
+            _stream_handle(dev)))
+    return found, out_nsym, out_cfo
+
+
+def _derotation_words(cfo_bins: torch.Tensor, step: int) -> torch.Tensor:
+    """``floor(-c * 2**32 / step)`` in int64 on the device, wrapped into int32: the ``impair`` word
+    that takes ``c`` bins (c cycles per symbol) off a slot."""
+    w = torch.div(-cfo_bins.to(torch.int64) * (1 << 32), int(step), rounding_mode="floor") & 0xFFFFFFFF
+    return torch.where(w >= 1 << 31, w - (1 << 32), w).to(torch.int32)
+
+
+def _receive_preamble_rows(plan: DemodPlan, rows: torch.Tensor, max_symbols, preamble_acc, hop, sync, thresh_up_db,
+                           thresh_dn_db, max_cfo_bins, first, capacity, cand_capacity, soft: bool = False,
+                           max_flips: int = 5) -> StreamPackets:
+    """The steps of ``receive_preamble_frames_device`` on [R, L] rows (checked by the caller)."""
+    from . import codec
+
+    sf, step, dev = plan.sf, plan.step, plan.device
+    max_symbols = int(max_symbols)
+    if max_symbols < 8:
+        raise ValueError("max_symbols must be >= 8: a frame has at least its header's eight symbols")
+    N, step, k, tail, max_cfo_bins = _preamble_geometry(hop, sf, plan.osr, preamble_acc, max_cfo_bins, plan.bw)
+    thresh_up_db = preamble_threshold_db(sf) if thresh_up_db is None else float(thresh_up_db)
+    thresh_dn_db = preamble_threshold_db(sf) if thresh_dn_db is None else float(thresh_dn_db)
+    R, L = rows.shape
+    up = plan.scan_acc(rows, hop, preamble_acc)
+    dn = plan.scan_acc(rows, hop, 2, conj=True)
+    ccount, cstarts, ccfo = find_preamble_device(up, dn, hop, sf, plan.osr, preamble_acc, thresh_up_db, thresh_dn_db,
+                                                 max_cfo_bins, L, cand_capacity, plan.bw)
+    C = cstarts.shape[1]
+    rs = rows.stride(0) if R > 1 else L
+    flat = rows.as_strided(((R - 1) * rs + L,), (1,)) if R else rows.reshape(-1)
+    row0 = (torch.arange(R, device=dev) * rs)[:, None]
+
+    def cut_slots(starts, cfo, data_len, cut):
+        """[sync | data] of every slot - 2 * step samples at start, data_len at start + 2 * step +
+        tail, zeros up to cut - with the slot's offset taken off (phase 0 at its first sample; the
+        gather skips the delimiter, so the derotation's phase steps at the join, which the
+        demodulator, non-coherent across symbols, does not see)."""
+        at = torch.where(starts >= 0, starts + row0, starts).reshape(-1)
+        buf = torch.empty((at.shape[0], cut + (cut & 1)), dtype=torch.complex64, device=dev)[:, :cut]
+        gather_frames_device(flat, at, torch.full_like(at, 2 * step), 2 * step, out=buf[:, :2 * step])
+        gather_frames_device(flat, torch.where(at >= 0, at + (2 * step + tail), at), data_len, cut - 2 * step,
+                             out=buf[:, 2 * step:])
+        return impair(buf, cfo=_derotation_words(cfo.reshape(-1), step), out=buf)
+
+    if R * C:
+        heads = cut_slots(cstarts, ccfo, torch.full((R * C,), 8 * step, dtype=torch.int64, device=dev), 10 * step)
+        if soft:
+            hdr = codec.decode_header_soft(plan.soft_bits(heads, plan.run(heads), reduced=(2, 8))[:, 2:], sf,
+                                           max_flips=max_flips)
+        else:
+            hdr = codec.decode_header(plan.run(heads).symbols, sf)
+        status, hsym = hdr.status.view(R, C), hdr.nsym.view(R, C)
+    else:
+        status = hsym = torch.empty((R, C), dtype=torch.int32, device=dev)
+    found, nsym, cfo_bins = select_preamble_device(cstarts, ccfo, status, hsym, step, L, max_symbols, first, capacity,
+                                                   tail)
+    cap = found.starts.shape[1]
+    max_bytes = codec.frame_capacity(sf, max_symbols)
+    if R * cap == 0:
+        none = {k_: torch.empty(0, dtype=torch.int32, device=dev) for k_ in codec.FrameResult._FIELDS}
+        frames = codec.FrameResult(payload=torch.empty((0, max_bytes), dtype=torch.uint8, device=dev), **none)
+        return StreamPackets(found, nsym, _no_frames(max_symbols, dev), frames, ccount, None, cfo_bins)
+    slots = cut_slots(found.starts, cfo_bins, nsym.reshape(-1).to(torch.int64) * step, (2 + max_symbols) * step)
+    res = plan.run(slots)
+    if soft:
+        llr = plan.soft_bits(slots, res, reduced=(2, 8))
+        frames = codec.decode_frame_soft(llr[:, 2:], sf, avail=nsym.reshape(-1), max_bytes=max_bytes,
+                                         max_flips=max_flips)
+        return StreamPackets(found, nsym, res, frames, ccount, llr, cfo_bins)
+    frames = codec.decode_frame(res.symbols, sf, avail=nsym.reshape(-1), max_bytes=max_bytes)
+    return StreamPackets(found, nsym, res, frames, ccount, None, cfo_bins)
+
+
+def receive_preamble_frames_device(plan: DemodPlan, iq: torch.Tensor, max_symbols: int, preamble_acc: int = 6,
+                                   hop: Optional[int] = None, sync: int = 0x12,
+                                   thresh_up_db: Optional[float] = None, thresh_dn_db: Optional[float] = None,
+                                   max_cfo_bins: Optional[int] = None,
+                                   first: Union[None, int, torch.Tensor] = None, capacity: Optional[int] = None,
+                                   cand_capacity: Optional[int] = None, soft: bool = False,
+                                   max_flips: int = 5) -> StreamPackets:
+    """``receive_frames_device`` for preambled frames (``modulate_preamble``,
+    ``LoRaMod.work_frame(preamble=...)``) under an integer carrier offset, without the host.  The
+    steps: two accumulating scans (``plan.scan_acc(rows, hop, preamble_acc)`` and ``plan.scan_acc(rows,
+    hop, 2, conj=True)``); ``find_preamble_device``; the header probe - two gathers into one buffer,
+    ``2 * step`` samples at each start and ``8 * step`` at ``start + 2 * step + tail``, empty slots
+    staying negative, then ``impair(buf, cfo=words, out=buf)`` with ``words = floor(-c * 2**32 /
+    step)`` wrapped into int32, one per slot - ``plan.run``; ``codec.decode_header`` (or its soft
+    form); ``select_preamble_device`` with the tail; the same two gathers at ``(2 + max_symbols) *
+    step`` with ``nsym * step`` of data; derotation, ``plan.run``, ``codec.decode_frame`` (or soft).
+    Nothing is read back and nothing synchronises.
+
+    ``thresh_up_db`` and ``thresh_dn_db`` default to ``preamble_threshold_db(sf)``, the measured choice
+    (-10 dB at SF7 to -22 dB at SF 11-12): lower values find no more frames at the default
+    ``cand_capacity``, because a frame's own data symbols then fill the candidate list.
+    ``preamble_acc`` (2..8) must not exceed the transmitter's preamble length; ``hop`` defaults to
+    ``step // 4`` and must divide ``step`` at least four times; ``max_cfo_bins`` defaults to ``N / 4
+    - 1``.  Returns StreamPackets with ``cfo_bins`` [R, capacity], each frame's offset in bins; the
+    residual fraction of a bin stays with the demodulator's own estimate (``result.cfo``).  The
+    ``sync`` word is the demodulator's to report (``result.sync``): the preamble finder does not
+    use it.  Limits: bw 125 kHz, SF 7-12, this project's own frame layout, one workgroup per row
+    in the finder kernels."""
+    if not plan.dechirp:
+        raise ValueError("receive_preamble_frames_device needs a plan with dechirp=True: the finder reads "
+                         "dechirped peaks")
+    if not isinstance(iq, torch.Tensor) or iq.dim() not in (1, 2):
+        raise ValueError("receive_preamble_frames_device takes one [L] stream or [R, L] rows")
+    hop = plan.step // 4 if hop is None else int(hop)
+    return _receive_preamble_rows(plan, _check_iq(iq, plan.device), max_symbols, preamble_acc, hop, sync, thresh_up_db,
+                                  thresh_dn_db, max_cfo_bins, first, capacity, cand_capacity, soft, max_flips)
+
+
+def receive_wideband_preamble_frames_device(plan: DemodPlan, chan: "Channelizer", iq: torch.Tensor, max_symbols: int,
+                                            preamble_acc: int = 6, hop: Optional[int] = None, sync: int = 0x12,
+                                            thresh_up_db: Optional[float] = None,
+                                            thresh_dn_db: Optional[float] = None,
+                                            max_cfo_bins: Optional[int] = None, scale: Optional[float] = None,
+                                            first: Union[None, int, torch.Tensor] = None,
+                                            capacity: Optional[int] = None, cand_capacity: Optional[int] = None,
+                                            soft: bool = False, max_flips: int = 5) -> StreamPackets:
+    """``receive_preamble_frames_device`` for a wideband capture: ``chan.run`` on the [L] complex64
+    stream (or the raw [L, 2] integer stream, converted with ``scale``), then the same steps over
+    the [C, Wc] channel rows, as ``receive_wideband_frames_device``.  No synchronisation."""
+    if not plan.dechirp:
+        raise ValueError("receive_wideband_preamble_frames_device needs a plan with dechirp=True: the finder reads "
+                         "dechirped peaks")
+    if not isinstance(iq, torch.Tensor) or iq.dim() != (2 if _is_raw(iq) else 1):
+        raise ValueError("receive_wideband_preamble_frames_device takes one [L] stream (raw samples: [L, 2])")
+    if chan.device != plan.device:
+        raise ValueError(f"the channelizer is on {chan.device}, the plan is on {plan.device}")
+    hop = plan.step // 4 if hop is None else int(hop)
+    rows = chan.run(iq, scale=scale)  # [C, Wc]
+    return _receive_preamble_rows(plan, rows, max_symbols, preamble_acc, hop, sync, thresh_up_db, thresh_dn_db,
+                                  max_cfo_bins, first, capacity, cand_capacity, soft, max_flips)
 
 
 def gather_frames_device(iq: torch.Tensor, at: torch.Tensor, length: torch.Tensor, cut: int,
