@@ -707,8 +707,10 @@ int64_t lora_synthesize_raw_batch(const float* in, int64_t rows, int64_t chan_le
  * A sample's value depends on (seed, R, n) and its row's parameters alone - not on chunking,
  * row count, alignment or which lane computed it: one call over a row equals, bit for bit, any
  * split of it into calls with first_sample advanced, and likewise for rows and first_row.
- * Not covered: a fractional delay, multipath, frequency drift, and DC offset, IQ imbalance or any
- * other front-end effect.  An integer delay is the caller's slice.
+ * A fractional delay, multipath, frequency drift and a sample-clock offset are
+ * lora_propagate_batch's, the stage in front of this one.  Not covered by either: DC offset, IQ
+ * imbalance or any other front-end effect, and time-varying path gains.  An integer delay is the
+ * caller's slice.
  *
  * Both entries enqueue one kernel on `stream` of `device`, allocate and synchronise nothing,
  * need no workspace and write samples 0 .. row_len-1 of every row and nothing else.  rows == 0
@@ -726,6 +728,74 @@ int64_t lora_impair_raw_batch(const float* in, int64_t rows, int64_t row_len, in
                               int64_t first_sample, int64_t first_row, uint64_t seed, const float* gain,
                               const int32_t* fcw, const int32_t* phase, const float* sigma, void* out, int format,
                               float inv_scale, int64_t out_stride, int device, void* stream);
+
+/* Propagation: what stands between the synthesis bank and the impairment stage.  Rows of
+ * complex64 in, rows of complex64 out: every output is the sum of `paths` paths, each the
+ * recording read at a fractional position - a delay, slid by a sample-clock offset - through a
+ * table of 256 fractional-delay filters and weighted by a complex gain; then a carrier offset
+ * that may drift.  One kernel; this definition, like the impairment's, is the library's own.
+ *   in     `rows` rows of `in_len` complex samples, row r at in + 2*r*in_stride floats (device).
+ *          Element j of a row is sample in_first + j of the recording; every sample of the
+ *          recording outside [in_first, in_first + in_len) reads as (+0, +0).  NULL is allowed
+ *          with in_len == 0;
+ *   out    `rows` rows of `row_len` samples: output t of row r is sample r*out_stride + t of out
+ *          (device) and is sample n = first_sample + t of the received recording.  out must not
+ *          overlap in: this is a filter, not a map;
+ *   paths  P, 1..8;  delay [rows][P] int64 (device), the delay of each path in units of 2^-32
+ *          sample, |delay| <= 2^47;  gain [rows][P][2] fp32 (device), (re, im) of each path;
+ *   sfo    [rows] int64 (device) or NULL (0): the sample-clock offset in units of 2^-32 sample
+ *          per sample, |sfo| <= 2^20 (about 244 ppm);
+ *   table  [256][taps] fp32 (device), the fractional-delay interpolator: row ph delays by
+ *          taps/2 - 1 + ph/256 samples.  taps = T is even, 2..32;
+ *   fcw, rate  [rows] int64 (device) or NULL: the carrier offset in units of fs / 2^64 and its
+ *          drift in units of fs / 2^64 per sample;  phase [rows] int32 (device) or NULL: the
+ *          starting phase, one step 2 pi / 2^32.
+ * first_sample >= 0, in_first >= 0, first_sample + row_len <= 2^40, in_first <= 2^41 (a clock
+ * offset moves the last positions 2^28 samples past 2^40), row_len < 2^31.  in and out need only be aligned to one sample.
+ * The position, for row r, path p and output n, all in int64 (the limits exclude overflow):
+ *     m  = -(delay[r][p] + sfo[r] * n)
+ *     q  = m >> 32  (arithmetic, i.e. floor)      fr = (uint32)m      ph = fr >> 24
+ *     j0 = n + q - (T/2 - 1)
+ * so the path reads the recording at x = n + q + fr / 2^32, truncated to a 256th of a sample.
+ * The sum, all fp32, one rounding per operation, no contraction, in this order, re(j) and im(j)
+ * being sample j of the recording:
+ *     sr = si = +0
+ *     for t = 0 .. T-1:   sr = sr + table[ph][t] * re(j0 + t)     si = si + table[ph][t] * im(j0 + t)
+ *     cr = gr*sr - gi*si            ci = gr*si + gi*sr
+ * and over the paths, from yr = yi = +0, for p = 0 .. P-1:   yr = yr + cr     yi = yi + ci.
+ * The rotation is performed only if one of fcw, rate, phase is given, a missing one counting as 0:
+ *     tri = n(n-1)/2 modulo 2^64: whichever of n, n-1 is even is halved, then the two are
+ *           multiplied modulo 2^64 (n = 0: 0)
+ *     W   = ((uint64)(uint32)phase[r] << 32) + (uint64)fcw[r] * n + (uint64)rate[r] * tri  mod 2^64
+ *     th  = (float)(int32)(W >> 32) * K           (s, c) = sincosf(th)
+ *     yr' = yr*c - yi*s             yi' = yr*s + yi*c
+ * with lora_impair_batch's K and sincosf: with rate == NULL and fcw = (int64)fcw32 << 32 the
+ * rotation is lora_impair_batch's bit for bit.
+ * Infinities and NaN in `in` propagate as this arithmetic makes them (a zero coefficient times
+ * an infinity is a NaN), with lora_channelize_batch's caveat about a NaN's sign and payload.
+ * A sample's value depends on (n, its row's parameters, the recording) alone: one call equals,
+ * bit for bit, any split of it into calls with first_sample advanced, and a call on any `in`
+ * window that still covers the taps of every path.
+ * delay and sfo live on the device, so their ranges cannot be checked here: they are the
+ * caller's contract (lora_phy_amd.stream checks them on the host).  Beyond them the samples are
+ * not this definition's, but nothing outside `in`'s window and `out`'s rows is touched.
+ * Not covered: time-varying path gains, and DC offset, IQ imbalance or any other front-end
+ * effect.  The quantiser is lora_impair_raw_batch, which follows this stage.
+ *
+ * Enqueues one kernel on `stream` of `device`, allocates and synchronises nothing, needs no
+ * workspace and writes samples 0 .. row_len-1 of every row and nothing else.  rows == 0 or
+ * row_len == 0: no launch.  LORA_EINVAL, before any HIP call, first rule first: negative rows,
+ * in_len, in_stride, in_first, row_len, first_sample or out_stride; row_len >= 2^31;
+ * first_sample + row_len > 2^40 or in_first > 2^41; with more than one row an in_stride smaller
+ * than in_len or an out_stride smaller than row_len; an in or out that is not aligned to one
+ * sample; in and out that overlap; paths outside 1..8; taps odd or outside 2..32; with work to
+ * do a NULL delay, gain, table or out, or a NULL in with in_len > 0; a grid beyond 2^31 (rows *
+ * ceil((row_len + 1) / 1024)).  Returns row_len. */
+int64_t lora_propagate_batch(const float* in, int64_t rows, int64_t in_len, int64_t in_stride, int64_t in_first,
+                             int64_t row_len, int64_t first_sample, int64_t paths, const int64_t* delay,
+                             const float* gain, const int64_t* sfo, const float* table, int64_t taps,
+                             const int64_t* fcw, const int64_t* rate, const int32_t* phase, float* out,
+                             int64_t out_stride, int device, void* stream);
 
 /* lora_modulate for `frames` independent frames: symbols [frames][sym_count] ->
  * iq [frames][(sym_count+2)*N*osr] (2 sync up-chirps then one chirp per symbol,

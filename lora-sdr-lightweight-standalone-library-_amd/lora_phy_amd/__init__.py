@@ -14,12 +14,12 @@ from ._capi import LoraError
 from .demod import (DemodPlan, DemodResult, DetectMetrics, LoRaDemod, SpecTrace, compensate_offsets,
                     spec_pipeline)
 from .mod import LoRaMod, modulate, modulate_preamble, preamble_tables
-from .stream import cfo_word, impair, noise_sigma
+from .stream import cfo_word, impair, noise_sigma, propagate
 
 __all__ = ["DemodPlan", "DemodResult", "DetectMetrics", "SpecTrace", "LoRaDemod", "LoRaMod", "LoraError", "modulate",
            "modulate_preamble", "preamble_tables",
            "compensate_offsets", "spec_pipeline", "codec", "codes", "iq_io", "phy", "shard", "stream", "lib_path", "version", "source_hash",
-           "check_build", "impair", "cfo_word", "noise_sigma"]
+           "check_build", "impair", "cfo_word", "noise_sigma", "propagate"]
 
 
 def lib_path() -> str:

@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = (
     "lora_synthesize_raw_batch",
     "lora_impair_batch",
     "lora_impair_raw_batch",
+    "lora_propagate_batch",
     "lora_mod_batch",
     "lora_estimate_offsets_batch",
     "lora_compensate_offsets_batch",
@@ -301,6 +302,13 @@ def lib() -> C.CDLL:
     L.lora_impair_raw_batch.restype = C.c_int64
     L.lora_impair_raw_batch.argtypes = (L.lora_impair_batch.argtypes[:12] + [C.c_int, C.c_float] +
                                         L.lora_impair_batch.argtypes[12:])
+    # the propagation stage (csrc/lora_propagate.hip): delay, gain, sfo, table, fcw, rate and phase
+    # are device arrays (sfo, fcw, rate and phase may be NULL)
+    L.lora_propagate_batch.restype = C.c_int64
+    L.lora_propagate_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                       C.c_void_p]
     L.lora_mod_batch.restype = C.c_int64
     L.lora_mod_batch.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_float, C.c_uint8, C.c_void_p,
                                  C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]

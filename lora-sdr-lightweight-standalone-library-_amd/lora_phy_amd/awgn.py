@@ -417,7 +417,7 @@ def sweep_receive_preamble(sf: int, snr_dbs: Sequence[float], frames: int = 1000
                            cfo_bins: float = 0.0, max_cfo_bins: Optional[int] = None, seed: int = 1234,
                            frames_per_row: int = 4, noise_windows: int = 0, noise_batch_samples: int = 1 << 26,
                            sync: int = 0x12, device=None, soft: bool = False, max_flips: int = 5,
-                           cand_capacity_mult: int = 1) -> List[Dict]:
+                           cand_capacity_mult: int = 1, propagate: Optional[Dict] = None) -> List[Dict]:
     """``sweep_receive_frames`` for preambled frames: what ``stream.receive_preamble_frames_device``
     returns under ``stream.impair`` with a carrier offset of ``cfo_bins`` bins.  The payloads, their
     lengths and the gaps are drawn from ``seed`` in ``sweep_receive_frames``' order, so the two
@@ -429,7 +429,16 @@ def sweep_receive_preamble(sf: int, snr_dbs: Sequence[float], frames: int = 1000
     it).  The noise-only record counts the candidates of the preamble finder.
     ``cand_capacity_mult``: the candidate capacity as a multiple of the chain's default (one slot
     per four symbols of the row), to tell frames lost to a full candidate list from frames not
-    found; ``candidates_dropped`` counts against the capacity used."""
+    found; ``candidates_dropped`` counts against the capacity used.
+
+    ``propagate``: a dict of ``stream.propagate`` keyword arguments (host values: ``delay`` a scalar,
+    [P] or [R, P], ``sfo_ppm`` and ``cfo`` scalars or one per row), applied once to the clean rows
+    before the SNR loop; the records then carry it as ``"propagate"``.  With ``None`` nothing is
+    applied and every record is what it was, bit for bit.  A channel moves a frame, so with one a
+    planted frame counts as found when a returned start lies within one chip (``osr`` samples) of
+    ``planted + delay + sfo * planted`` - ``delay`` the first path's and ``sfo`` the clock offset as
+    a fraction - instead of on the planted sample itself, and ``cfo_right`` asks for
+    ``round(cfo_bins + cfo * step)``."""
     from . import codec, stream
     from .mod import modulate_preamble
 
@@ -463,9 +472,34 @@ def sweep_receive_preamble(sf: int, snr_dbs: Sequence[float], frames: int = 1000
     live = torch.arange(rows.shape[1], device=dev)[None, :] < torch.from_numpy(length).to(dev).reshape(-1, 1)
     clean.view(-1)[(at[:, None] + torch.arange(rows.shape[1], device=dev))[live]] = rows[live]
     del rows, live
+    want_c = int(round(float(cfo_bins)))
+    moved_t = None
+    if propagate is not None:
+        # the scoring needs the channel's numbers on the host: tensors and shapes it cannot read are refused
+        for k in ("delay", "sfo_ppm", "cfo"):
+            if isinstance(propagate.get(k), torch.Tensor):
+                raise TypeError(f"propagate[{k!r}] must be a host value here: the scoring reads it")
+        d0 = np.asarray(propagate.get("delay", 0.0), np.float64)
+        d0 = d0.reshape(1, 1) if d0.ndim == 0 else d0.reshape(1, -1) if d0.ndim == 1 else d0
+        if d0.ndim != 2 or d0.shape[0] not in (1, R) or d0.shape[1] < 1:
+            raise ValueError(f"propagate['delay'] must be a scalar, [P] or [{R}, P]")
+        sfo = propagate.get("sfo_ppm")
+        sfo = np.asarray(0.0 if sfo is None else sfo, np.float64)
+        if sfo.ndim > 1 or (sfo.ndim == 1 and sfo.shape[0] not in (1, R)):
+            raise ValueError(f"propagate['sfo_ppm'] must be a scalar or one value per row ([{R}])")
+        sfo = sfo.reshape(-1, 1) * 1e-6
+        c = propagate.get("cfo")
+        if c is not None:
+            if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, float, np.integer, np.floating)):
+                raise ValueError("propagate['cfo'] must be one number here (a float in cycles per sample, an int a "
+                                 "word): cfo_right asks for one offset")
+            cycles = float(c) / 18446744073709551616.0 if isinstance(c, (int, np.integer)) else float(c)
+            want_c = int(round(float(cfo_bins) + cycles * step))
+        clean = stream.propagate(clean, **propagate)
+        L = int(clean.shape[1])
+        moved_t = torch.from_numpy(np.broadcast_to(starts + d0[:, :1] + sfo * starts, starts.shape).copy()).to(dev)
     work = torch.empty_like(clean)
     W = (L - step) // hop + 1
-    want_c = int(round(float(cfo_bins)))
     counts = []
 
     mult = int(cand_capacity_mult)
@@ -478,7 +512,10 @@ def sweep_receive_preamble(sf: int, snr_dbs: Sequence[float], frames: int = 1000
     def tally(got):
         valid = got.found.valid                                                  # [R, cap]
         cap = valid.shape[1]
-        same = got.found.starts[:, :, None] == starts_t[:, None, :]              # [R, cap, K]
+        if moved_t is None:
+            same = got.found.starts[:, :, None] == starts_t[:, None, :]          # [R, cap, K]
+        else:
+            same = (got.found.starts[:, :, None].to(torch.float64) - moved_t[:, None, :]).abs() <= osr
         hit = same.any(2) & valid
         which = same.to(torch.int8).argmax(2)
         ok = got.frames.status.view(R, cap) == codec.FRAME_OK
@@ -516,6 +553,10 @@ def sweep_receive_preamble(sf: int, snr_dbs: Sequence[float], frames: int = 1000
     common = {"sf": sf, "osr": osr, "hop": hop, "thresh_up_db": float(thresh_up_db),
               "thresh_dn_db": float(thresh_dn_db), "preamble": P, "preamble_acc": int(preamble_acc),
               "cfo_bins": float(cfo_bins), "max_symbols": S, "cand_capacity_mult": mult}
+    if propagate is not None:
+        # (as JSON takes it: a complex gain as [re, im])
+        plain = lambda a: np.stack([a.real, a.imag], -1).tolist() if a.dtype.kind == "c" else a.tolist()  # noqa: E731
+        common["propagate"] = {k: plain(np.asarray(v)) for k, v in propagate.items()}
     for snr, (right, hit, false, false_ok, cands, dropped, cfo_right) in zip(snr_dbs, got.tolist()):
         out.append(dict(common, snr_db=float(snr), max_bytes=B, rdd=codes.rdd_of(cr), planted=F, returned_ok=right,
                         cfo_right=cfo_right, found_at_planted=hit, false_frames=false, false_frames_ok=false_ok,

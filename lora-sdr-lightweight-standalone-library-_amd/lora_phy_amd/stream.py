@@ -161,6 +161,16 @@ arithmetic is in include/lora_mi355x.h and is this project's own: the reference 
 synthesiser).  ``transmit_wideband`` places modulated frames in their channels and runs it, and
 ``LoRaMod.work_wideband`` modulates first.  Rational up-rates are not covered, and no
 spectral-mask or adjacent-channel figure is claimed.
+
+The channel.  Between a transmitter and a receiver stand ``propagate`` - up to eight paths, each a
+fractional delay through a table of 256 interpolating filters (``fracdelay_table``) times a complex
+gain, a sample-clock offset that slides the reading position and a carrier offset that may drift
+(lora_propagate_batch) - and then ``impair``: a gain, a carrier offset, counter-based white noise
+and, given a raw dtype, the quantiser (lora_impair_batch, lora_impair_raw_batch).  Both are one
+kernel each, defined to the bit in include/lora_mi355x.h as this project's own, reproducible in
+chunks, and restated in numpy (tests/propagate_checker.py, tests/impair_checker.py).  The
+composition is ``transmit_wideband`` -> ``propagate`` -> ``impair`` -> ``receive_*``.  Fading
+(time-varying gains) and front-end effects are not covered.
 """
 from __future__ import annotations
 
@@ -179,7 +189,8 @@ __all__ = ["find_frames", "extract_frames", "receive", "lowpass_taps", "nco_tabl
            "impair", "cfo_word", "noise_sigma", "gather_frames_device", "StreamPackets", "find_candidates_device",
            "select_frames_device", "receive_frames_device", "receive_wideband_frames_device",
            "preamble_threshold_db", "find_preamble_device", "select_preamble_device", "receive_preamble_frames_device",
-           "receive_wideband_preamble_frames_device"]
+           "receive_wideband_preamble_frames_device", "propagate", "fracdelay_table", "delay_word", "sfo_word",
+           "cfo_word64", "drift_word"]
 
 _NONE = -(1 << 62)  # "no candidate here" in the packed starts
 
@@ -1611,8 +1622,9 @@ def impair(iq: Optional[torch.Tensor], *, sigma=None, snr_db=None, amplitude=1.0
     127.5; ``scale`` without ``dtype`` is a ``ValueError``).  Returns the result.  One kernel on
     the current stream; it never synchronises and never reads device memory on the host.
 
-    Not covered: a fractional delay, multipath, frequency drift, and DC offset, IQ imbalance or
-    any other front-end effect; an integer delay is a slice."""
+    A fractional delay, multipath, a clock offset and frequency drift are ``propagate``'s, which
+    goes in front.  Not covered: DC offset, IQ imbalance or any other front-end effect, and
+    time-varying path gains; an integer delay is a slice."""
     if sigma is not None and snr_db is not None:
         raise ValueError("sigma and snr_db are mutually exclusive")
     if dtype is None:
@@ -1699,4 +1711,265 @@ def impair(iq: Optional[torch.Tensor], *, sigma=None, snr_db=None, amplitude=1.0
         got = lib.lora_impair_batch(*head, *tail_args)
     got = _capi.check(got)
     assert got == L, (got, L)
+    return out
+
+
+# ---- propagation: multipath, fractional delay, clock offset, drift (lora_propagate_batch) -------
+
+# The Kaiser beta of the default table: the value with the smallest worst-case response error over
+# all 256 phases and |f| <= 0.4 cycles per sample at 16 taps (DESIGN.md section 6q has the sweep)
+FRACDELAY_BETA = 5.05
+
+_MAX_DELAY_WORD = 1 << 47
+_MAX_SFO_WORD = 1 << 20
+_default_tables: dict = {}
+
+
+def fracdelay_table(taps: int = 16, beta: float = FRACDELAY_BETA) -> np.ndarray:
+    """``propagate``'s fractional-delay interpolator: [256, taps] float32, row ``ph`` a filter that
+    delays by ``taps/2 - 1 + ph/256`` samples.  A Kaiser-windowed sinc evaluated in float64:
+    ``u = t - (taps/2 - 1) - ph/256``, ``h = sinc(u) * I0(beta * sqrt(1 - (u / (taps/2))**2)) /
+    I0(beta)`` and zero where ``|u| > taps/2``; every row is normalised to sum 1 in float64 and then
+    rounded to fp32; row 0 is the exact unit impulse at ``t = taps/2 - 1``, so a whole-sample delay
+    is a copy.  ``taps`` is even, 2..32."""
+    taps = int(taps)
+    if taps < 2 or taps > 32 or taps % 2:
+        raise ValueError("taps must be even and in 2..32")
+    half = taps // 2
+    u = np.arange(taps, dtype=np.float64)[None, :] - (half - 1) - np.arange(256, dtype=np.float64)[:, None] / 256.0
+    z = 1.0 - (u / half) ** 2
+    h = np.where(z >= 0.0, np.sinc(u) * np.i0(float(beta) * np.sqrt(np.maximum(z, 0.0))) / np.i0(float(beta)), 0.0)
+    h /= h.sum(axis=1, keepdims=True)
+    table = h.astype(np.float32)
+    table[0] = 0.0
+    table[0, half - 1] = 1.0
+    return table
+
+
+def delay_word(samples: float) -> int:
+    """A delay in samples as ``propagate``'s word: ``round(samples * 2**32)``, to nearest with ties
+    to even (one step is 2**-32 sample).  ``|word| > 2**47`` (32768 samples) is a ``ValueError``."""
+    w = int(round(float(samples) * 4294967296.0))
+    if abs(w) > _MAX_DELAY_WORD:
+        raise ValueError("a delay is at most 2**15 samples either way")
+    return w
+
+
+def sfo_word(ppm: float) -> int:
+    """A sample-clock offset in parts per million as ``propagate``'s word: ``round(ppm * 1e-6 *
+    2**32)``, to nearest with ties to even (one step is 2**-32 sample per sample).  ``|word| >
+    2**20`` (about 244 ppm) is a ``ValueError``."""
+    w = int(round(float(ppm) * 1e-6 * 4294967296.0))
+    if abs(w) > _MAX_SFO_WORD:
+        raise ValueError("a sample-clock offset is at most 2**20 words (about 244 ppm) either way")
+    return w
+
+
+def _wrap64(w: int) -> int:
+    w &= (1 << 64) - 1
+    return w - (1 << 64) if w >= 1 << 63 else w
+
+
+def cfo_word64(cycles_per_sample: float) -> int:
+    """A carrier offset in cycles per sample as ``propagate``'s 64-bit frequency control word:
+    ``round(cycles_per_sample * 2**64)`` to nearest, wrapped into int64 (one step is fs / 2**64;
+    0.5 and -0.5 are the same word, -2**63).  ``cfo_word(c) << 32`` is ``impair``'s offset."""
+    c = float(cycles_per_sample)
+    if not np.isfinite(c):
+        raise ValueError("a carrier offset must be finite")
+    return _wrap64(int(round(c * 18446744073709551616.0)))
+
+
+def drift_word(hz_per_s: float, fs: float) -> int:
+    """A carrier drift in Hz per second at the sample rate ``fs`` (Hz) as ``propagate``'s word:
+    ``round(hz_per_s / fs**2 * 2**64)`` to nearest (one step is fs / 2**64 per sample).  A drift
+    whose word does not fit int64 (half a cycle per sample, per sample) is a ``ValueError``."""
+    fs = float(fs)
+    if not fs > 0.0 or not np.isfinite(float(hz_per_s)):
+        raise ValueError("fs must be positive and the drift finite")
+    w = int(round(float(hz_per_s) / (fs * fs) * 18446744073709551616.0))
+    if not -(1 << 63) <= w < 1 << 63:
+        raise ValueError("the drift does not fit the 64-bit word")
+    return w
+
+
+def _path_array(v, R: int, name: str):
+    """A per-path host value as a [1 or R, P] array: a scalar, [P] or [R, P]."""
+    a = np.asarray(v)
+    if a.ndim == 0:
+        a = a.reshape(1, 1)
+    elif a.ndim == 1:
+        a = a.reshape(1, -1)
+    if a.ndim != 2 or a.shape[0] not in (1, R) or a.shape[1] < 1:
+        raise ValueError(f"{name} must be a scalar, one value per path ([P]) or per row and path ([{R}, P])")
+    return a
+
+
+def _path_delay(v, R: int, dev: torch.device) -> torch.Tensor:
+    """``delay`` as [1 or R, P] int64 words on ``dev``: host values go through ``delay_word``, a
+    float tensor is rounded on the device, an int64 tensor is taken as words (a tensor's range is
+    its owner's contract: nothing is read back)."""
+    if isinstance(v, torch.Tensor):
+        if v.device != dev:
+            raise ValueError(f"delay is on {v.device}, the samples are on {dev}")
+        t = v.reshape(1, 1) if v.dim() == 0 else v.reshape(1, -1) if v.dim() == 1 else v
+        if t.dim() != 2 or t.shape[0] not in (1, R) or t.shape[1] < 1:
+            raise ValueError(f"delay must be a scalar, [P] or [{R}, P]")
+        return t if t.dtype == torch.int64 else torch.round(t.to(torch.float64) * 4294967296.0).to(torch.int64)
+    a = _path_array(v, R, "delay")
+    w = np.array([[delay_word(x) for x in row] for row in a.tolist()], np.int64)
+    return torch.from_numpy(w).to(dev)
+
+
+def _path_gain(v, R: int, dev: torch.device) -> torch.Tensor:
+    """``gain`` as [1 or R, P, 2] float32 (re, im) on ``dev``."""
+    if isinstance(v, torch.Tensor):
+        if v.device != dev:
+            raise ValueError(f"gain is on {v.device}, the samples are on {dev}")
+        t = v.reshape(1, 1) if v.dim() == 0 else v.reshape(1, -1) if v.dim() == 1 else v
+        if t.dim() != 2 or t.shape[0] not in (1, R) or t.shape[1] < 1:
+            raise ValueError(f"gain must be a scalar, [P] or [{R}, P]")
+        return torch.view_as_real(t.to(torch.complex64).contiguous())
+    a = _path_array(v, R, "gain").astype(np.complex64)
+    return torch.from_numpy(np.stack([a.real, a.imag], axis=-1).astype(np.float32)).to(dev)
+
+
+def _row_words64(v, R: int, dev: torch.device, name: str, conv) -> Optional[torch.Tensor]:
+    """A per-row 64-bit word parameter: None, or a contiguous [R] int64 tensor on ``dev``.  A
+    Python int or an int64 tensor is taken as words; a host float goes through ``conv``."""
+    if v is None:
+        return None
+    if isinstance(v, torch.Tensor):
+        if v.dim() > 1 or (v.dim() == 1 and v.shape[0] not in (1, R)):
+            raise ValueError(f"{name} must be a scalar or one value per row ([{R}])")
+        if v.device != dev:
+            raise ValueError(f"{name} is on {v.device}, the samples are on {dev}")
+        if v.dtype != torch.int64:
+            raise TypeError(f"a {name} tensor holds int64 words; give cycles as host values")
+        return (v.reshape(-1).expand(R) if v.numel() == 1 else v).contiguous()
+    a = np.asarray(v, dtype=object).reshape(-1)
+    if a.size not in (1, R):
+        raise ValueError(f"{name} must be a scalar or one value per row ([{R}])")
+    w = [int(x) if isinstance(x, (int, np.integer)) and not isinstance(x, bool) else conv(x) for x in a.tolist()]
+    if any(not -(1 << 63) <= x < 1 << 63 for x in w):
+        raise ValueError(f"a {name} word must fit int64")
+    return torch.from_numpy(np.broadcast_to(np.array(w, np.int64), (R,)).copy()).to(dev)
+
+
+def propagate(iq: torch.Tensor, *, delay=0.0, gain=1.0, sfo_ppm=None, cfo=None, drift=None, phase=None, table=None,
+              in_first: int = 0, first_sample: int = 0, length: Optional[int] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Propagation between a transmitter and a receiver, one kernel (lora_propagate_batch; the
+    exact arithmetic is in include/lora_mi355x.h and is this project's own): every output sample
+    is the sum of ``P`` paths, each the recording read ``delay`` samples earlier through a
+    fractional-delay interpolator and weighted by a complex ``gain``; the reading position slides
+    by ``sfo_ppm`` parts per million of a sample per sample (a transmitter whose sample clock is
+    slow by that much: a frame planted at sample ``s`` arrives near ``s + delay + sfo * s``); and
+    the sum is rotated by a carrier offset ``cfo`` (cycles per sample) that drifts by ``drift``
+    (cycles per sample, per sample: ``hz_per_s / fs**2``) from a starting ``phase`` (cycles), a
+    64-bit phase accumulator that is continuous across chunks by construction.
+
+    ``iq``: [L] or [R, L] complex64 CUDA samples (unit sample stride, rows that do not overlap),
+    element ``j`` being sample ``in_first + j`` of the clean recording; whatever lies outside
+    reads as zero.  The result is [length] or [R, length] (default ``L``), element ``t`` being
+    sample ``first_sample + t`` of the received recording: a recording propagated in chunks, each
+    from a window of ``iq`` that covers its paths' taps, is bit for bit the recording propagated
+    at once.  ``out``: a complex64 tensor of the result's shape to write into; it must not share
+    memory with ``iq``.
+
+    ``delay`` and ``gain``: a scalar, one value per path ([P]) or per row and path ([R, P]); the
+    two broadcast against each other.  Host delays are in samples (``delay_word``; negative is an
+    advance); an int64 tensor on the device is taken as words, a float tensor is rounded there,
+    and a tensor's range (``|delay| <= 2**15`` samples) is the caller's contract, since nothing
+    is read back.  ``sfo_ppm``: a scalar or one value per row, host values in parts per million
+    (``sfo_word``); a tensor on the device as a delay tensor is - int64 holds words of 2**-32 sample
+    per sample, a float tensor parts per million rounded there, its range (``|sfo| <= 2**20``
+    words) the caller's contract.  ``cfo`` and
+    ``drift``: a scalar or one per row, floats through ``cfo_word64`` (``drift`` is the same unit
+    per sample; ``drift_word`` converts Hz per second), Python ints and int64 tensors as words.
+    ``phase``: as ``impair``'s.  The rotation with ``drift=None`` is ``impair``'s bit for bit when
+    ``cfo`` is a multiple of 2**-32.  ``table``: [256, taps] float32, numpy or on the device
+    (default ``fracdelay_table()``, kept per device).
+
+    One kernel on the current stream; it never synchronises and never reads device memory on the
+    host.  The channel of a simulated link is ``transmit_wideband`` (or ``modulate_preamble``) ->
+    ``propagate`` -> ``impair`` (noise, and the quantiser when ``dtype`` is given) ->
+    ``receive_*``; ``propagate``'s ``cfo`` and ``impair``'s add.
+
+    Not covered: time-varying path gains, and DC offset, IQ imbalance or any other front-end
+    effect."""
+    _require_cuda(iq, "iq")
+    one = iq.dim() == 1
+    dev = iq.device
+    x = _check_iq(iq, dev)
+    R, L = x.shape
+    W = L if length is None else int(length)
+    in_first, first_sample = int(in_first), int(first_sample)
+    if W < 0 or in_first < 0 or first_sample < 0:
+        raise ValueError("length, in_first and first_sample must be >= 0")
+    if W >= 1 << 31 or first_sample + W > 1 << 40 or in_first > 1 << 41:
+        raise ValueError("length must be < 2**31, first_sample + length <= 2**40 and in_first <= 2**41")
+    d_t, g_t = _path_delay(delay, R, dev), _path_gain(gain, R, dev)
+    P = max(d_t.shape[1], g_t.shape[1])
+    if d_t.shape[1] not in (1, P) or g_t.shape[1] not in (1, P) or not 1 <= P <= 8:
+        raise ValueError("delay and gain must agree on the number of paths, 1..8")
+    d_t = d_t.expand(R, P).contiguous()
+    g_t = g_t.expand(R, P, 2).contiguous()
+    if sfo_ppm is None:
+        s_t = None
+    elif isinstance(sfo_ppm, torch.Tensor):
+        # as a delay tensor: int64 holds words, a float tensor parts per million, rounded on the device
+        if sfo_ppm.dtype != torch.int64:
+            if not sfo_ppm.is_floating_point():
+                raise TypeError("an sfo_ppm tensor is int64 (words of 2**-32 sample per sample) or floating (ppm)")
+            sfo_ppm = torch.round(sfo_ppm.to(torch.float64) * (1e-6 * 4294967296.0)).to(torch.int64)
+        s_t = _row_words64(sfo_ppm, R, dev, "sfo_ppm", sfo_word)
+    else:
+        a = np.asarray(sfo_ppm, np.float64).reshape(-1)
+        if a.size not in (1, R):
+            raise ValueError(f"sfo_ppm must be a scalar or one value per row ([{R}])")
+        s_t = torch.from_numpy(np.broadcast_to(np.array([sfo_word(v) for v in a.tolist()], np.int64), (R,)).copy())
+        s_t = s_t.to(dev)
+    f_t = _row_words64(cfo, R, dev, "cfo", cfo_word64)
+    r_t = _row_words64(drift, R, dev, "drift", cfo_word64)
+    p_t = _row_values(phase, R, dev, "phase", True)
+    if table is None:
+        key = (dev.type, dev.index)
+        if key not in _default_tables:
+            _default_tables[key] = torch.from_numpy(fracdelay_table()).to(dev)
+        tab = _default_tables[key]
+    elif isinstance(table, torch.Tensor):
+        if table.device != dev or table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
+            raise ValueError(f"table must be a contiguous float32 [256, taps] tensor on {dev}")
+        tab = table
+    else:
+        tab = torch.from_numpy(np.ascontiguousarray(table, np.float32)).to(dev)
+    if tab.dim() != 2 or tab.shape[0] != 256 or tab.shape[1] < 2 or tab.shape[1] > 32 or tab.shape[1] % 2:
+        raise ValueError("table must be [256, taps] with taps even and in 2..32")
+    lead = () if one else (R,)
+    if out is None:
+        out = torch.empty(lead + (W,), dtype=torch.complex64, device=dev)
+    else:
+        _require_cuda(out, "out")
+        if out.dtype != torch.complex64:
+            raise TypeError("out must be complex64")
+        ok = out.device == dev and tuple(out.shape) == lead + (W,)
+        if ok and W > 1:
+            ok = out.stride(len(lead)) == 1
+        if ok and R > 1 and not one:
+            ok = out.stride(0) >= W
+        if not ok:
+            raise ValueError(f"out must be a complex64 {list(lead + (W,))} tensor on {dev} with unit stride within "
+                             "a row and rows that do not overlap")
+    if R == 0 or W == 0:
+        return out  # nothing to launch (and an empty tensor has no address to pass)
+    in_stride = x.stride(0) if R > 1 else L
+    out_stride = out.stride(0) if (not one and R > 1) else W
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    got = _capi.lib().lora_propagate_batch(x.data_ptr() if L else None, R, L, in_stride, in_first, W, first_sample, P,
+                                           d_t.data_ptr(), g_t.data_ptr(), ptr(s_t), tab.data_ptr(), tab.shape[1],
+                                           ptr(f_t), ptr(r_t), ptr(p_t), out.data_ptr(), out_stride, dev.index,
+                                           _stream_handle(dev))
+    got = _capi.check(got)
+    assert got == W, (got, W)
     return out
