@@ -90,6 +90,38 @@ def test_lora_demodulate(O, R, sf, osr):
                 assert u32(a[2]) == u32(b[2]) and u32(a[3]) == u32(b[3])
 
 
+@pytest.mark.parametrize("sf,osr,hann", [(7, 1, False), (10, 1, True), (8, 2, False)])
+def test_lora_demodulate_short_scratch(O, R, sf, osr, hann):
+    """LoRaDemod.cpp:68-71: a frame whose maximum is > 1 needs the scratch buffer to rescale
+    into; with a null or shorter one the call returns 0 and writes nothing.  Amplitude > 1 with
+    scratch_len of count - 1, count and 0 (a null pointer in the reference's shim), and
+    amplitude exactly 1.0 with scratch_len 0 (no rescaling, so no scratch needed)."""
+    rng = np.random.default_rng(900 + sf)
+    N = 1 << sf
+    count = 6 * N * osr + 3
+    syms = rng.integers(0, N, 4).astype(np.uint16)
+    x = np.concatenate([R.lora_modulate(syms, sf, osr, 125000, 1.0, 0x12), np.zeros(3, np.complex64)])
+    x = O.dechirp((x + 0.1 * (rng.standard_normal(count) + 1j * rng.standard_normal(count))).astype(np.complex64),
+                  sf, osr)
+    peak = max(np.abs(x.real).max(), np.abs(x.imag).max())
+    loud = (x * np.float32(2.5 / peak)).astype(np.complex64)
+    unit = (x * np.float32(0.5 / peak)).astype(np.complex64)
+    unit.real[count // 2] = np.float32(1.0)
+    assert max(np.abs(unit.real).max(), np.abs(unit.imag).max()) == 1.0
+    assert max(np.abs(loud.real).max(), np.abs(loud.imag).max()) > 1.0
+    for frame, scratch_len, refused in ((loud, count - 1, True), (loud, count, False), (loud, 0, True),
+                                        (unit, 0, False)):
+        a = O.lora_demodulate(frame, sf, osr, hann, scratch_len=scratch_len)
+        b = R.lora_demodulate(frame, sf, osr, hann, scratch_len=scratch_len)
+        np.testing.assert_array_equal(a[0], b[0])
+        assert a[1] == b[1]
+        assert u32(a[2]) == u32(b[2]) and u32(a[3]) == u32(b[3])
+        if refused:  # nothing written: the wrappers' zeroed outputs stay
+            assert len(a[0]) == 0 and a[1] == 0 and u32(a[2]) == 0 and u32(a[3]) == 0
+        else:
+            assert len(a[0]) == 4 and u32(a[2]) != 0
+
+
 @pytest.mark.parametrize("sf", [2, 5, 7, 8, 10, 12])
 @pytest.mark.parametrize("osr", [1, 3])
 def test_api_demodulate_estimate_compensate(O, R, sf, osr):
